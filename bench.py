@@ -12,10 +12,12 @@ kernel per filter step forward and one backward (dx + per-image parameter gradie
 64x512x512x3 fp16 NHWC batch already resident in HBM.  Multi-GPU: images are independent, so
 ranks hold disjoint replicas of the batch shape (weak scaling, no data-path collective).
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` for the
-dominant kernel (HIP-event timed, algorithmic bytes: 12 B/px fwd, 18 B/px bwd at fp16) and
-`cpu_baseline` (the torch-CPU fp32 op-by-op restatement, oracle/filters_torch.py, timed on the
-host cores on a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `ms_per_step`, ...); with --full the chain line also carries `roofline` for the
+dominant kernel (HIP-event timed, algorithmic bytes: 12 B/px fwd, 18 B/px bwd at fp16, + `hbm_cold`), the extra
+`legs` (64x64x64x3 chain, training iteration, all-reduce) and `cpu_baseline` (the C / OpenMP and torch-CPU fp32
+restatements, oracle/, timed on the host cores on a bounded sample, + a parity check against the float64 oracle).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; see dump_chain_outputs).
 """
 import argparse
 import json
@@ -43,14 +45,14 @@ def parse():
   ap.add_argument('--warmup', type=int, default=5)
   ap.add_argument('--shape', default=None, help='A|B|C (synthetic.SHAPES) or N,H,W; default C (chain), B (infer)')
   ap.add_argument('--dtype', default='f16', choices=['f16', 'f32'])
-  ap.add_argument('--kernel-reps', type=int, default=50, help='launches per kernel for the roofline timing')
+  ap.add_argument('--kernel-reps', type=int, default=50, help='launches per kernel for the roofline timing (--full)')
   ap.add_argument('--prewarm-s', type=float, default=0.3, help='untimed clock warm-up before the W warm-up steps')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baseline')
   ap.add_argument('--rotating-probe', action='store_true',
                   help='also time the dominant kernel back to back on operands rotating through three buffer sets '
                   '(roofline.avg_launch_ms_rotating_buffers)')
-  ap.add_argument('--no-per-kernel', action='store_true')
-  ap.add_argument('--no-legs', action='store_true', help='skip the extra legs of the default line (64x64x64 chain, training '
+  ap.add_argument('--no-per-kernel', action='store_true', help='--full without the per-kernel roofline')
+  ap.add_argument('--no-legs', action='store_true', help='skip the extra legs of the --full line (64x64x64 chain, training '
                   'iteration, all-reduce): profiling runs that want the chain kernels only')
   ap.add_argument('--seed', type=int, default=1234)
   ap.add_argument('--order', default='0,1,2,3,4,5,6,7', help='filter ids of the chain steps (experiments only; the '
@@ -69,7 +71,15 @@ def parse():
                   "the 256 MiB Infinity Cache) for roofline.hbm_cold; 'none' disables")
   ap.add_argument('--graph', default='auto', choices=['auto', 'on', 'off'],
                   help='replay the 17 launches of a step from one hipGraph (auto = on; off: eager C-ABI calls)')
-  return ap.parse_args()
+  ap.add_argument('--full', action='store_true',
+                  help='chain workload: after the headline also measure the per-kernel roofline (+ hbm_cold), the extra '
+                  'legs and the CPU baseline with its parity check (a plain run times the headline only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='chain workload: write what the last timed step computed as DIR/<name>.npy (float32)')
+  args = ap.parse_args()
+  if args.dump_outputs and args.workload != 'chain':
+    ap.error('--dump-outputs is implemented for the chain workload only')
+  return args
 
 
 def parse_shape(name):
@@ -158,6 +168,36 @@ class Chain:
       self.graph.replay()
     for _ in range(steps % self.unroll):
       self.launch()
+
+
+DUMP_SAMPLE = 1 << 20  # values kept per output tensor: 9 tensors x 4 MiB + the parameter gradients stay below 64 MB
+
+
+def dump_chain_outputs(chain, out_dir):
+  """What the caller of the timed path receives from its last step, as float32 .npy files in `out_dir`: the output of
+  every chain step (fwd_out_<k>, k = 0 .. steps-1; the last one is the processed image), the gradient with respect to the
+  input image (dx) and every step's per-image parameter gradients (dparams_<k>, whole).  An image tensor larger than
+  DUMP_SAMPLE values is reduced to the same fixed, seeded sample of flat indices (sorted) in every run with the same
+  shape.  Every step recomputes the same values from the same inputs, so the last step's outputs are these."""
+  os.makedirs(out_dir, exist_ok=True)
+  torch.cuda.synchronize()
+  nsteps = len(chain.ids)
+  numel = chain.acts[0].numel()
+  idx = None
+  if numel > DUMP_SAMPLE:
+    idx = np.unique(np.random.default_rng(20240611).integers(0, numel, DUMP_SAMPLE))
+    idx = torch.from_numpy(idx).to(chain.acts[0].device)
+
+  def sample(t):
+    flat = t.reshape(-1)
+    return (flat if idx is None else flat.index_select(0, idx)).float().cpu().numpy()
+
+  outs = {'fwd_out_%d' % k: sample(chain.acts[k + 1]) for k in range(nsteps)}
+  outs['dx'] = sample(chain.grads[0])
+  outs.update({'dparams_%d' % k: chain.dparams[k].float().cpu().numpy() for k in range(nsteps)})
+  for name, arr in outs.items():
+    np.save(os.path.join(out_dir, name + '.npy'), arr)
+  return sum(a.nbytes for a in outs.values())
 
 
 def time_kernels(chain, reps):
@@ -1325,7 +1365,11 @@ def main():
       },
   }
 
-  if rank == 0 and not args.no_per_kernel:
+  if rank == 0 and args.dump_outputs:
+    nbytes = dump_chain_outputs(chain, args.dump_outputs)
+    print('outputs of the last timed step: %.1f MB in %s' % (nbytes / 1e6, args.dump_outputs), file=sys.stderr)
+  # everything below measures or checks beyond the headline: --full only
+  if args.full and rank == 0 and not args.no_per_kernel:
     per = time_kernels(chain, args.kernel_reps)
     dom = max(per, key=per.get)
     bpp = (2 if dom.startswith('fwd') else 3) * 3 * esz  # algorithmic bytes per pixel per launch
@@ -1388,7 +1432,7 @@ def main():
       if cold is not None:
         result['roofline']['hbm_cold'] = cold
   barrier()
-  if not args.no_legs and os.environ.get('EXPO_BENCH_LEGS', '1') != '0':
+  if args.full and not args.no_legs and os.environ.get('EXPO_BENCH_LEGS', '1') != '0':
     try:
       del chain  # (rank 0 may already have dropped it in front of the cold leg)
     except NameError:
@@ -1410,7 +1454,7 @@ def main():
         'allreduce_bus_GBps': legs.get('allreduce', {}).get('bus_GBps'),
         'errors': {k: v['error'] for k, v in legs.items() if isinstance(v, dict) and 'error' in v} or None,
     }
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
     result['cpu_baseline'] = cpu_baseline()
     try:
       result['cpu_baseline']['parity_check'] = parity_sample(dev)

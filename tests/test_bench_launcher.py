@@ -56,3 +56,48 @@ def test_traffic_is_null_for_a_shape_without_a_pmc_pass():
   assert bench.load_traffic('bwd_C', (64, 64, 64, 3), 'f16') is None
   assert bench.load_traffic('bwd_C', (64, 512, 512, 3), 'f32') is None
   assert bench.load_traffic('bwd_C', (64, 512, 512, 3), 'f16') > 3e8
+
+
+def test_dump_outputs_is_refused_outside_the_chain_workload():
+  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run', '--workload', 'train',
+                        '--dump-outputs', 'unused'], capture_output=True, text=True, timeout=300)
+  assert out.returncode == 2 and 'chain workload only' in out.stderr, out.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_dumps_its_last_step(tmp_path, gpu_device):
+  """A plain run prints the headline only (the roofline, the legs and the CPU baseline are --full), and --dump-outputs
+  writes what its last timed step computed: the values one direct call of the library computes on the same seeded
+  case."""
+  import numpy as np
+  import torch
+  sys.path.insert(0, ROOT)
+  import bench
+  env = dict(os.environ)
+  for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+    env.pop(k, None)
+  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--shape', 'A', '--dump-outputs', str(tmp_path)], env=env, cwd=ROOT, capture_output=True,
+                       text=True, timeout=600)
+  assert out.returncode == 0, out.stderr[-3000:]
+  lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+  assert len(lines) == 1, out.stdout[-2000:]
+  d = json.loads(lines[0])
+  assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0
+  assert d['unit'] == 'Mpixels/s' and d['higher_is_better'] is True and d['dtype'] == 'f16'
+  assert not {'roofline', 'per_kernel', 'legs', 'cpu_baseline'} & set(d), sorted(d)
+  chain = bench.Chain(bench.parse_shape('A'), torch.float16, gpu_device, 1234)
+  chain.launch()
+  torch.cuda.synchronize()
+  want = {'fwd_out_%d' % k: chain.acts[k + 1] for k in range(8)}
+  want['dx'] = chain.grads[0]
+  want.update({'dparams_%d' % k: chain.dparams[k] for k in range(8)})
+  assert sorted(p.name for p in tmp_path.iterdir()) == sorted(name + '.npy' for name in want)
+  for name, t in want.items():
+    got = np.load(str(tmp_path / (name + '.npy')))
+    assert got.dtype == np.float32, name
+    ref = t.float().cpu().numpy()
+    if name.startswith('dparams'):
+      np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-6, err_msg=name)
+    else:  # shape A is below the sample size: the whole tensor, flattened
+      np.testing.assert_array_equal(got, ref.reshape(-1), err_msg=name)

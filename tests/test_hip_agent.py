@@ -618,7 +618,7 @@ def test_bench_workloads_under_the_driver_launch_line(workload, gpu_device):
          os.path.join(root, 'bench.py'), '--gpus', '1', '--workload', workload,
          '--steps', '5', '--warmup', '2', '--shape', 'B']
   if workload == 'chain':
-    cmd += ['--no-cpu-baseline', '--cold-shape', 'none']
+    cmd += ['--full', '--no-cpu-baseline', '--cold-shape', 'none']
   out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
   assert out.returncode == 0, out.stderr[-3000:]
   lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -626,7 +626,7 @@ def test_bench_workloads_under_the_driver_launch_line(workload, gpu_device):
   d = json.loads(lines[0])
   assert d['n_gpus'] == 1 and d['steps'] == 5 and d['warmup'] == 2 and d['value'] > 0 and d['unit'] == 'Mpixels/s'
   assert d['scaling'] == 'weak' and d['data'] == 'synthetic' and 'roofline' in d
-  if workload == 'chain':  # the default line's extra legs under a (1-rank) RCCL process group
+  if workload == 'chain':  # the --full line's extra legs under a (1-rank) RCCL process group
     assert 'error' not in d['legs'] and 'error' not in d['legs']['train'] and 'allreduce' not in d['legs'], d['legs']
     assert d['legs']['train']['roofline']['flops_per_iteration'] > 1e11
 

@@ -151,7 +151,7 @@ def test_bench_launches_two_ranks_that_share_the_gpu(gpu_device):
     env.pop(k, None)
   for extra in (['--scaling', 'weak', '--shape', 'B'], ['--scaling', 'strong', '--shape', 'B', '--no-legs']):
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
-                          '--no-cpu-baseline', '--cold-shape', 'none'] + extra, env=env, cwd=ROOT, capture_output=True,
+                          '--full', '--no-cpu-baseline', '--cold-shape', 'none'] + extra, env=env, cwd=ROOT, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -164,7 +164,7 @@ def test_bench_launches_two_ranks_that_share_the_gpu(gpu_device):
     if '--no-legs' in extra:
       assert 'legs' not in d
       continue
-    # the extra legs of the default line, run by BOTH ranks after the timed region: config 2's shape, one training
+    # the extra legs of the --full line, run by BOTH ranks after the timed region: config 2's shape, one training
     # iteration with its gradient exchange, the gradient buckets' all-reduce alone
     legs = d['legs']
     assert 'error' not in legs, legs

@@ -11,11 +11,11 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 db() { find "$1" -name "*.db" | head -1; }
 COLD=256,512,512
-Q="--no-cpu-baseline --cold-shape none --no-legs"
+Q="--full --no-cpu-baseline --cold-shape none --no-legs"
 
 # the gpu suite, recording the worst |err| / A of every reduced-quantity comparison (tests/_tol.py)
 EXPO_RECORD_PARAM_ERR=$OUT/param_grad_errors.jsonl python -m pytest $R/tests -x -q -m gpu 2>&1 | tail -2 > $OUT/pytest_gpu.txt
-python $R/bench.py > $OUT/bench_chain.json 2> $OUT/bench_chain.err
+python $R/bench.py --full > $OUT/bench_chain.json 2> $OUT/bench_chain.err
 EXPO_CHAIN_STREAMS=1 python $R/bench.py $Q > $OUT/bench_chain_1stream.json 2>/dev/null
 python $R/bench.py --shape A $Q > $OUT/bench_chain_A.json 2>/dev/null
 python $R/bench.py --shape B $Q > $OUT/bench_chain_B.json 2>/dev/null

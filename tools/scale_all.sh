@@ -13,7 +13,7 @@ NG=$(python -c "import torch; print(torch.cuda.device_count())")
 # rehearsal on a 1-GPU box: EXPO_BENCH_SHARE_GPU=1 lets the ranks share the GPU over gloo (bench.py); the table then
 # shows the plumbing works, its numbers mean nothing
 [ "${EXPO_BENCH_SHARE_GPU:-0}" = 1 ] && NG=${EXPO_SCALE_MAX_RANKS:-2}
-Q="--no-cpu-baseline --no-per-kernel --cold-shape none"
+Q="--full --no-cpu-baseline --no-per-kernel --cold-shape none"
 for n in 1 2 4 8; do
   [ $n -gt $NG ] && break
   for sc in weak strong; do
