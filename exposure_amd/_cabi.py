@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # never a non-HIP implementation.
 LIB_PATH = os.environ.get('EXPO_HIP_LIB') or os.path.join(_HERE, 'libexposure_hip.so')
 
-EXPO_ABI_VERSION = 7
+EXPO_ABI_VERSION = 8
 EXPO_CURVE_MAX_STEPS = 16
 EXPO_F16, EXPO_F32 = 0, 1
 EXPO_MAX_PARAMS = 24
@@ -46,6 +46,7 @@ SIGNATURES = {
     'expo_filter_dispatch_fwd': (_i, [_vp, _vp, _vp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_filter_dispatch_bwd': (_i, [_vp, _vp, _vp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_chain_streams': (_i, [_i, _i, _i, _i]),
+    'expo_chain_plan': (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     'expo_chain_helper_stats': (_i, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'expo_chain_prepare': (_i, [_vp]),
     'expo_conv4x4s2_fwd': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _vp]),
@@ -892,6 +893,20 @@ def curve_bwd(x, dy, dx, params, dparams, curves, steps, workspace=None):
 def chain_streams(n, h, w, dtype_code):
   """1 or 2: how many streams expo_chain_fwd / _bwd use for a batch of this shape."""
   return int(load().expo_chain_streams(int(n), int(h), int(w), int(dtype_code)))
+
+
+def chain_plan(n, h, w, dtype_code):
+  """The plan expo_chain_fwd / _bwd run for a batch of this shape (expo_chain_plan; read-only):
+  (chunks, lanes, snake) with chunks = [(first image, image count, lane), ...] in launch order, lane 0 = the caller's
+  stream and 1 = the helper, lanes = 1 or 2, snake = True when alternate launches walk the images in reverse."""
+  lib = load()
+  lanes, snake = ctypes.c_int(0), ctypes.c_int(0)
+  args = (int(n), int(h), int(w), int(dtype_code))
+  count = lib.expo_chain_plan(*args, None, 0, None, None)
+  _check(min(count, 0), 'expo_chain_plan')
+  buf = (ctypes.c_int * max(3 * count, 1))()
+  _check(min(lib.expo_chain_plan(*args, buf, count, ctypes.byref(lanes), ctypes.byref(snake)), 0), 'expo_chain_plan')
+  return [tuple(buf[3 * c:3 * c + 3]) for c in range(count)], lanes.value, bool(snake.value)
 
 
 def chain_helper_stats():

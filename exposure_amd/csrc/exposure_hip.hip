@@ -2274,6 +2274,21 @@ int expo_chain_streams(int n, int h, int w, int dtype) {
   return chain_plan(n, h, w, dtype).two_lanes ? 2 : 1;
 }
 
+int expo_chain_plan(int n, int h, int w, int dtype, int* chunks, int max_chunks, int* lanes, int* snake) {
+  if (int rc = check_common(n, h, w, dtype)) return rc;
+  if (max_chunks < 0 || (max_chunks > 0 && !chunks)) return fail(EXPO_E_BADARG, "bad chunk buffer");
+  if (n == 0) return 0;  // the chain entry points return before planning
+  const ChainPlan plan = chain_plan(n, h, w, dtype);
+  for (size_t c = 0; c < plan.chunks.size() && int(c) < max_chunks; ++c) {
+    chunks[3 * c] = plan.chunks[c].nb;
+    chunks[3 * c + 1] = plan.chunks[c].np;
+    chunks[3 * c + 2] = plan.chunks[c].lane;
+  }
+  if (lanes) *lanes = plan.two_lanes ? 2 : 1;
+  if (snake) *snake = plan.snake ? 1 : 0;
+  return int(plan.chunks.size());
+}
+
 int expo_chain_prepare(void* stream) {
   // The probe of DESIGN.md 3.5 as an explicit initialisation step: an integrator who does not want the first eager
   // two-stream chain call of `stream` to stall that stream (one one-wave kernel waiting <= 0.5 ms per candidate, two

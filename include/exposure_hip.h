@@ -48,12 +48,12 @@
 extern "C" {
 #endif
 
-#define EXPO_ABI_VERSION 7 /* 2: caller-owned reduction workspace (no float atomics, no fills); 3: derivatives of the
+#define EXPO_ABI_VERSION 8 /* 2: caller-owned reduction workspace (no float atomics, no fills); 3: derivatives of the
                               critic statistics and of the penalty, VignetFilter, bias + lrelu, masked per-image dispatch;
                               4: Tone / Color curves of any cfg.curve_steps (expo_curve_*); 5: the convnets' convolution
                               (expo_conv4x4s2_*); 6: its mask / bias variants, the hand-scheduled critic update's
                               kernels, expo_build_info; 7: expo_net_inputs, the first FC layer with its K dimension split
-                              (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums) */
+                              (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -236,6 +236,17 @@ int expo_finish_bwd(const int* filter_ids, int steps, const float* const* params
  * -3.5 % per step at 64x512x512).  Nothing changes for the caller: all work is ordered after what `stream` held
  * before the call and before what it receives afterwards, and the pattern is capturable into a hipGraph.
  * expo_chain_streams() returns the number of streams (1 or 2) a shape gets (EXPO_CHAIN_STREAMS=1|2 overrides).
+ * A tensor of 256 MiB or more (EXPO_CHAIN_TILE_MIN_MIB) runs TILE-MAJOR instead: every step on one tile of images
+ * (EXPO_CHAIN_TILE_MIB per tensor, balanced: tile sizes differ by at most one image) before the next, each tile split
+ * over the two streams when a tile of the smaller size would be.  Consecutive launches walk the images in alternating
+ * order for an untiled tensor of 256 MiB or more (EXPO_CHAIN_SNAKE=0|1 overrides; EXPO_CHAIN_SNAKE is IGNORED when the
+ * batch is tiled).
+ *
+ * (ABI 8) expo_chain_plan() reports the plan expo_chain_fwd / _bwd run for a shape, read-only (it launches nothing and
+ * touches no stream): the return value is the number of chunks C (0 for n == 0; a negative EXPO_E_* on invalid
+ * arguments), the first min(C, max_chunks) chunks are written to chunks[3 k .. 3 k + 2] = (first image, image count,
+ * lane: 0 = `stream`, 1 = the helper) in launch order, *lanes = 1 or 2, *snake = 1 when alternate launches walk the
+ * images in reverse.  chunks may be NULL when max_chunks is 0; lanes and snake may be NULL.
  *
  * The helper is chosen per (device, caller stream) and must sit on another hardware queue than `stream`: the pairing
  * is probed ONCE per caller stream (two one-wave kernels, < 0.1 ms; a rejected helper costs 0.5 ms -- the kernel on
@@ -251,6 +262,7 @@ int expo_finish_bwd(const int* filter_ids, int steps, const float* const* params
  * process probed and how many helpers it rejected (diagnostics; either pointer may be NULL).
  */
 int expo_chain_streams(int n, int h, int w, int dtype);
+int expo_chain_plan(int n, int h, int w, int dtype, int* chunks, int max_chunks, int* lanes, int* snake);
 int expo_chain_helper_stats(int* probed, int* rejected);
 int expo_chain_prepare(void* stream);
 int expo_chain_release(void* stream);

@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 
+import numpy as np
 import pytest
 import torch
 
@@ -74,6 +75,28 @@ def test_argument_validation_without_gpu():
   assert lib.expo_vignet_apply_fwd(None, None, None, 1.0, 1, 1, 4, 4, 5, None) == -2
   assert lib.expo_bias_lrelu_fwd(None, None, None, 0, 1, 0.2, None) == 0
   assert lib.expo_bias_lrelu_fwd(None, None, None, 8, 1, 0.2, None) == -1
+
+
+def test_chain_plan_query_without_gpu():
+  """expo_chain_plan is host logic (no launch): the default plans of tests/test_hip_chain_plans.py's in-process cases,
+  the one-lane and two-lane sizes, and the argument checks."""
+  f16, f32 = _cabi.EXPO_F16, _cabi.EXPO_F32
+  tiled = lambda sizes: [c for at, tn in zip(np.cumsum([0] + sizes[:-1]), sizes)
+                         for c in ((int(at), tn // 2, 0), (int(at) + tn // 2, tn - tn // 2, 1))]
+  assert _cabi.chain_plan(256, 512, 512, f16) == (tiled([64] * 4), 2, False)
+  assert _cabi.chain_plan(190, 512, 512, f16) == (tiled([64, 63, 63]), 2, False)
+  assert _cabi.chain_plan(128, 512, 512, f32) == (tiled([32] * 4), 2, False)
+  assert _cabi.chain_plan(27, 512, 512, f16) == ([(0, 13, 0), (13, 14, 1)], 2, False)
+  assert _cabi.chain_plan(64, 64, 64, f16) == ([(0, 64, 0)], 1, False)
+  assert _cabi.chain_plan(1, 8192, 8192, f16) == ([(0, 1, 0)], 1, True)  # 384 MiB in one image: untiled, reversed
+  for n, h, w, dt in ((256, 512, 512, f16), (27, 512, 512, f16), (16, 512, 512, f16), (7, 33, 31, f16)):
+    assert _cabi.chain_streams(n, h, w, dt) == _cabi.chain_plan(n, h, w, dt)[1]
+  lib = _cabi.load()
+  assert lib.expo_chain_plan(0, 4, 4, f16, None, 0, None, None) == 0
+  assert lib.expo_chain_plan(4, 0, 4, f16, None, 0, None, None) == -1
+  assert lib.expo_chain_plan(4, 4, 4, 7, None, 0, None, None) == -2
+  assert lib.expo_chain_plan(4, 4, 4, f16, None, 1, None, None) == -1  # a count without a buffer
+  assert lib.expo_chain_plan(256, 512, 512, f16, None, 0, None, None) == 8  # the count alone
 
 
 def test_product_path_refuses_cpu_tensors():

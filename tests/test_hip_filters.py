@@ -533,7 +533,8 @@ def test_empty_batch_and_error_paths(gpu_device):
 
 def test_single_huge_image_offsets(gpu_device):
   """One 16384 x 16384 fp16 image (1.5 GiB): byte offsets close to the 32-bit limit of the buffer
-  resource.  Checked through identities and a sampled oracle comparison at the far end."""
+  resource.  Checked through identities, a sampled oracle comparison at the far end, and float64 references of the
+  backward: Tone's parameter gradient and the tail's dx (C oracle), Exposure's (a float64 sum on the device)."""
   dev = gpu_device
   h = w = 16384
   g = torch.Generator(device=dev).manual_seed(1)
@@ -552,6 +553,40 @@ def test_single_huge_image_offsets(gpu_device):
   dp = torch.empty_like(k)
   _cabi.filter_bwd(4, x, x, y, k, dp)  # dy := x, dx -> y
   assert torch.isfinite(dp).all() and torch.isfinite(y[:, tail].float()).all()
+  # the float64 C oracle over bands of rows: Tone's parameter gradient is a sum over the pixels (its per-image factors
+  # depend on the parameters only), so the bands' dp and A add up; dx of the last band's tail rows pixel by pixel
+  from oracle import filters_c as fc
+  try:
+    ncpu = len(os.sched_getaffinity(0))
+  except (AttributeError, OSError):
+    ncpu = os.cpu_count() or 1
+  fc.set_threads(max(1, min(64, ncpu // 2)), np.float64)
+  k64 = k.cpu().numpy().astype(np.float64)
+  ref_dp, ref_a = np.zeros_like(k64), np.zeros_like(k64)
+  band = 1024
+  for r0 in range(0, h, band):
+    xb = x[:, r0:r0 + band].cpu().numpy().astype(np.float64)
+    rdx, rdp, adp = fc.backward_packed(4, xb, k64, xb, with_abs=True)
+    ref_dp += rdp
+    ref_a += adp
+  del xb
+  assert_image_close(y[:, tail].float().cpu().numpy(), rdx[:, -2:], np.float16, 'tone dx of the last rows')
+  del rdx
+  assert_param_grad_close(dp.cpu().numpy(), ref_dp, ref_a, 'tone dparams of a 16384 x 16384 image')
+  # one light filter (Exposure: four groups per thread at >= 256 MiB, 1024 blocks at most): dEV = ln2 sum dy x 2^EV
+  # against a float64 sum on the device
+  ev = torch.tensor([[0.7]], device=dev)
+  dy = torch.randn((1, h, w, 3), device=dev, generator=g, dtype=torch.float16)
+  dev_grad = torch.full_like(ev, float('nan'))
+  _cabi.filter_bwd(0, x, dy, None, ev, dev_grad)
+  ref = torch.zeros((), dtype=torch.float64, device=dev)
+  scale = torch.zeros((), dtype=torch.float64, device=dev)
+  for r0 in range(0, h, band):
+    t = dy[:, r0:r0 + band].double() * x[:, r0:r0 + band].double() * (2.0**float(ev.item()) * np.log(2.0))
+    ref += t.sum()
+    scale += t.abs().sum()
+  assert_param_grad_close(dev_grad.cpu().numpy(), ref.cpu().numpy().reshape(1, 1), scale.cpu().numpy().reshape(1, 1),
+                          'exposure dEV of a 16384 x 16384 image')
 
 
 def test_random_shape_sweep(gpu_device):
