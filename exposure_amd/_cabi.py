@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # never a non-HIP implementation.
 LIB_PATH = os.environ.get('EXPO_HIP_LIB') or os.path.join(_HERE, 'libexposure_hip.so')
 
-EXPO_ABI_VERSION = 8
+EXPO_ABI_VERSION = 9
 EXPO_CURVE_MAX_STEPS = 16
 EXPO_F16, EXPO_F32 = 0, 1
 EXPO_MAX_PARAMS = 24
@@ -81,6 +81,8 @@ SIGNATURES = {
     'expo_chain_bwd': (_i, [ctypes.POINTER(_i), _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                             ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_chain_fused_fwd': (_i, [_vp, _fp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'expo_chain_fused_fwd_ragged': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i),
+                                         ctypes.POINTER(_i), _i, _i, _vp]),
     'expo_chain_fused_bwd': (_i, [_vp, _fp, _i, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_critic_stats': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_overexposure_penalty': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -467,6 +469,46 @@ def chain_fused_fwd(filter_ids, params, x, y):
   with torch.cuda.device(x.device):
     _check(lib.expo_chain_fused_fwd(_ptr(filter_ids), _ptr(params), steps, _ptr(x), _ptr(y), n, h, w,
                                     _dtype_code(x), _stream()), 'expo_chain_fused_fwd')
+
+
+def chain_fused_fwd_ragged(filter_ids, params, xs, ys):
+  """``chain_fused_fwd`` over a list of images of different sizes in one launch: xs / ys lists of N contiguous device
+  tensors, (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype and device; ys[i] has xs[i]'s shape.  filter_ids (N, steps)
+  int32, params (N, steps, 24) float32: row i is image i's sequence.  (The per-image checks are the host cost of this
+  call, ~1-2 us per image: kept to a few attribute reads each.)"""
+  lib = load()
+  n = len(xs)
+  if len(ys) != n:
+    raise ExposureHipError('exposure_amd: xs and ys must have the same length')
+  if filter_ids.dim() != 2 or filter_ids.shape[0] != n or not filter_ids.is_cuda or filter_ids.dtype != torch.int32 or \
+      not filter_ids.is_contiguous():
+    raise ExposureHipError('exposure_amd: filter_ids must be a contiguous int32 device tensor of shape (N, steps)')
+  steps = filter_ids.shape[1]
+  _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
+  if n == 0:
+    return
+  dt, dev = xs[0].dtype, filter_ids.get_device()
+  if params.get_device() != dev:
+    raise ExposureHipError('exposure_amd: filter_ids and params must be on the images\' device')
+  hs, ws = [0] * n, [0] * n
+  for i in range(n):
+    x, y = xs[i], ys[i]
+    if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)):
+      raise ExposureHipError('exposure_amd: xs[%d] / ys[%d] must be tensors' % (i, i))
+    sx = x.shape
+    if sx != y.shape or sx[-1] != 3 or not (len(sx) == 3 or (len(sx) == 4 and sx[0] == 1)):
+      raise ExposureHipError('exposure_amd: xs[%d] %s / ys[%d] %s must both be (H, W, 3) or (1, H, W, 3)' %
+                             (i, tuple(sx), i, tuple(y.shape)))
+    if x.dtype is not dt or y.dtype is not dt or x.get_device() != dev or y.get_device() != dev:
+      raise ExposureHipError('exposure_amd: every image must be a ROCm device tensor of one dtype, on the device of '
+                             'filter_ids (HIP path only, no CPU fallback)')
+    if not (x.is_contiguous() and y.is_contiguous()):
+      raise ExposureHipError('exposure_amd: xs[%d] / ys[%d] must be contiguous' % (i, i))
+    hs[i], ws[i] = sx[-3], sx[-2]
+  with torch.cuda.device(dev):
+    _check(lib.expo_chain_fused_fwd_ragged(_ptr(filter_ids), _ptr(params), steps, _ptr_array(xs), _ptr_array(ys),
+                                           (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]),
+                                           _stream()), 'expo_chain_fused_fwd_ragged')
 
 
 FUSED_BWD_MAX_STEPS = 8  # EXPO_FUSED_BWD_MAX_STEPS

@@ -30,26 +30,20 @@ namespace expo {
 // ------------------------------------------------------- fused multi-step forward (inference)
 // The high-resolution inference path (net.py:796-821; BASELINE config 5): the per-step parameters
 // are regressed on the 64x64 proxy only, so by the time the full-resolution image is touched the
-// whole per-image sequence (filter id, parameters) x steps is known.  This kernel applies all
+// whole per-image sequence (filter id, parameters) x steps is known.  These kernels apply all
 // `steps` filters to a pixel group while it sits in registers (fp32 between steps -- no fp16
 // rounding of intermediates): ONE read and ONE write of the image instead of one per step.
 // Each wave owns exactly one 3 KiB chunk, so the per-step parameters are fetched once per wave
 // through scalar loads; the step loop is rolled (block-uniform switch per step).
-template <typename T, bool VEC, class IO>
-__global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd_kernel(const int32_t* __restrict__ ids,
-                                                                   const float* __restrict__ params, int steps,
-                                                                   const T* __restrict__ x, T* __restrict__ y,
-                                                                   int hw, int groups) {
+//
+// chain_fused_run is that step loop for the PPL pixels of one group (v, fp32, in place): image sequence idn[steps] /
+// prn[steps][EXPO_MAX_PARAMS] (wave-uniform), `tab` this wave's curve table in LDS, `plane` the parameter this lane
+// mirrors for the curve builds.  Shared by the dense kernel (one (N, H, W, 3) tensor) and the ragged one (a list of
+// images of any sizes).
+template <typename T>
+__device__ inline void chain_fused_run(const int32_t* idn, const float* prn,
+                                                int steps, float2_lut* tab, int plane, float* v) {
   constexpr int PPL = PixTraits<T>::PPL;
-  const int n = blockIdx.y;
-  const size_t off = size_t(n) * hw * 3;
-  const T* xi = x + off;
-  T* yi = y + off;
-  const int32_t* idn = ids + size_t(n) * steps;
-  const float* prn = params + size_t(n) * steps * EXPO_MAX_PARAMS;
-  __shared__ float2_lut curve_tab[kWaves][32];
-  float2_lut* const tab = curve_tab[threadIdx.x >> 6];
-  const int plane = (threadIdx.x & 63) % EXPO_MAX_PARAMS;  // which parameter this lane mirrors
   // One step, OUT OF PLACE (in -> out).  The step loop below runs two steps per trip with the two pixel arrays (and
   // the two parameter sets) swapping roles, so no loop-carried value is ever copied: the rolled one-step loop paid 24
   // v_mov + 24 s_mov per step for its loop PHIs (the coupled filters cannot update a pixel in place), ~17 % of the
@@ -89,43 +83,84 @@ __global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd
     }
 #undef EXPO_CASE
   };
-  auto run = [&](float* v) {
-    // software-pipelined parameter fetch: a step's id and 24 parameters (wave-uniform -> scalar loads into SGPRs)
-    // are requested one step ahead, hiding the scalar-load latency; `k*` is a per-lane copy (lane l <-> parameter l)
-    // for the curve table.  Two parameter sets alternate like the pixel arrays.
-    float pa[EXPO_MAX_PARAMS], pb[EXPO_MAX_PARAMS];
-    float ka = 0.f, kb = 0.f;
-    int ia = 0, ib = 0;
-    // a step past the end (the second half of the last trip of an odd-length sequence) is the identity: Exposure with
-    // 0 EV, x * 2^0 = x exactly -- no extra case in the switch
-    auto fetch = [&](int st, float* p, float& kl, int& id) {
-      const bool live = st < steps;
-      const int sn = live ? st : steps - 1;  // (past the end: any valid row)
-      id = live ? idn[sn] : 0;
-      kl = prn[sn * EXPO_MAX_PARAMS + plane];
+  // software-pipelined parameter fetch: a step's id and 24 parameters (wave-uniform -> scalar loads into SGPRs)
+  // are requested one step ahead, hiding the scalar-load latency; `k*` is a per-lane copy (lane l <-> parameter l)
+  // for the curve table.  Two parameter sets alternate like the pixel arrays.
+  float pa[EXPO_MAX_PARAMS], pb[EXPO_MAX_PARAMS];
+  float ka = 0.f, kb = 0.f;
+  int ia = 0, ib = 0;
+  // a step past the end (the second half of the last trip of an odd-length sequence) is the identity: Exposure with
+  // 0 EV, x * 2^0 = x exactly -- no extra case in the switch
+  auto fetch = [&](int st, float* p, float& kl, int& id) {
+    const bool live = st < steps;
+    const int sn = live ? st : steps - 1;  // (past the end: any valid row)
+    id = live ? idn[sn] : 0;
+    kl = prn[sn * EXPO_MAX_PARAMS + plane];
 #pragma unroll
-      for (int j = 0; j < EXPO_MAX_PARAMS; ++j) p[j] = prn[sn * EXPO_MAX_PARAMS + j];
-      if (!live) p[0] = 0.0f;
-    };
-    if (steps <= 0) return;
-    // (the pixel arrays are locals, copied in and out -- free in SSA form.  Running the loop directly on the caller's
-    // array made hipcc 7.2 allocate the fp32 kernel's store ADDRESS register inside the 96-bit data tuple of the first
-    // pixel row: R and G of every 64th pixel wrong.  Caught by the fp32 parity tests, gpurun r03p17;
-    // tests/test_isa_sanity.py now scans every kernel's ISA for that overlap.)
-    float a[PPL * 3], w[PPL * 3];
-#pragma unroll
-    for (int j = 0; j < PPL * 3; ++j) a[j] = v[j];
-    fetch(0, pa, ka, ia);
-#pragma unroll 1
-    for (int st = 0; st < steps; st += 2) {
-      fetch(st + 1, pb, kb, ib);
-      apply(ia, pa, ka, a, w);
-      fetch(st + 2, pa, ka, ia);
-      apply(ib, pb, kb, w, a);
-    }
-#pragma unroll
-    for (int j = 0; j < PPL * 3; ++j) v[j] = a[j];
+    for (int j = 0; j < EXPO_MAX_PARAMS; ++j) p[j] = prn[sn * EXPO_MAX_PARAMS + j];
+    if (!live) p[0] = 0.0f;
   };
+  if (steps <= 0) return;
+  // (the pixel arrays are locals, copied in and out -- free in SSA form.  Running the loop directly on the caller's
+  // array made hipcc 7.2 allocate the fp32 kernel's store ADDRESS register inside the 96-bit data tuple of the first
+  // pixel row: R and G of every 64th pixel wrong.  Caught by the fp32 parity tests, gpurun r03p17;
+  // tests/test_isa_sanity.py now scans every kernel's ISA for that overlap.)
+  float a[PPL * 3], w[PPL * 3];
+#pragma unroll
+  for (int j = 0; j < PPL * 3; ++j) a[j] = v[j];
+  fetch(0, pa, ka, ia);
+#pragma unroll 1
+  for (int st = 0; st < steps; st += 2) {
+    fetch(st + 1, pb, kb, ib);
+    apply(ia, pa, ka, a, w);
+    fetch(st + 2, pa, ka, ia);
+    apply(ib, pb, kb, w, a);
+  }
+#pragma unroll
+  for (int j = 0; j < PPL * 3; ++j) v[j] = a[j];
+}
+
+// The pixel loop of one image's share of the grid: wave chunks first_gw, first_gw + stride, ... (VEC: the dwordx3
+// buffer path of pixel_io.h; otherwise the element-wise path, whose trip count is kept wave-uniform because the curve
+// builds need lanes 0..23 of every wave alive -- groups past the end load zeros and store nothing).
+template <typename T, bool VEC, class IO>
+__device__ __forceinline__ void chain_fused_image(const int32_t* idn, const float* prn, int steps, const T* xi, T* yi,
+                                                  int hw,
+                                                  int groups, int first_gw, int stride, float2_lut* tab) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int plane = (threadIdx.x & 63) % EXPO_MAX_PARAMS;  // which parameter this lane mirrors
+  auto run = [&](float* v) { chain_fused_run<T>(idn, prn, steps, tab, plane, v); };
+  if constexpr (VEC) {
+    const T* const ins[1] = {xi};
+    stream_groups<T, 1, true, false, IO>(ins, yi, hw, first_gw, stride,
+                                         [&](float (&v)[1][PPL * 3], int) { run(v[0]); });
+  } else {
+    for (int g0 = first_gw; g0 < groups; g0 += stride) {
+      const int g = g0 + (threadIdx.x & 63);
+      float v[PPL * 3];
+      load_slow<T>(xi, g, hw, v);
+      run(v);
+      store_slow<T>(yi, g, hw, v);
+    }
+  }
+}
+
+template <typename T, bool VEC, class IO>
+__global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd_kernel(const int32_t* __restrict__ ids,
+                                                                   const float* __restrict__ params, int steps,
+                                                                   const T* __restrict__ x, T* __restrict__ y,
+                                                                   int hw, int groups) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int n = blockIdx.y;
+  const size_t off = size_t(n) * hw * 3;
+  const T* xi = x + off;
+  T* yi = y + off;
+  const int32_t* idn = ids + size_t(n) * steps;
+  const float* prn = params + size_t(n) * steps * EXPO_MAX_PARAMS;
+  __shared__ float2_lut curve_tab[kWaves][32];
+  float2_lut* const tab = curve_tab[threadIdx.x >> 6];
+  const int plane = (threadIdx.x & 63) % EXPO_MAX_PARAMS;  // which parameter this lane mirrors
+  auto run = [&](float* v) { chain_fused_run<T>(idn, prn, steps, tab, plane, v); };
   const int stride = gridDim.x * kThreads;
   if constexpr (VEC) {
     const T* const ins[1] = {xi};
@@ -144,6 +179,52 @@ __global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd
   }
 }
 
+// ------------------------------------------------------- ragged: a list of images of any sizes in one launch
+// The chain is per pixel: an image matters to it through its base address and pixel count only.  The grid is 1-D
+// over the images' blocks laid end to end (image i: ceil(groups_i / kThreads) blocks, one chunk per wave as above);
+// the table of up to kRaggedMaxImages images travels BY VALUE in the kernel arguments (no library-owned device
+// memory, no copy; 1.6 KB of the 4 KB kernarg block), a call with more images is split into launches of that many.
+// A block finds its image by a binary search over `first` with the block index -- uniform, so the search, the
+// image's pointers, its pixel count and its ids / params row are all scalar.
+constexpr int kRaggedMaxImages = 64;
+template <typename T>
+struct RaggedTable {
+  const T* x[kRaggedMaxImages];
+  T* y[kRaggedMaxImages];
+  int hw[kRaggedMaxImages];
+  int first[kRaggedMaxImages + 1];  // first block of image i; first[n] = the grid's size
+  int n;
+  uint64_t vec;  // bit i: image i takes the dwordx3 path (the decision make_geom takes for one image)
+};
+
+// ANY_SLOW: some image of this launch needs the element-wise path (instantiated apart so that an all-vector launch
+// carries exactly the dense kernel's vector code and register budget)
+template <typename T, class IO, bool ANY_SLOW>
+__global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd_ragged_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ params, int steps, const RaggedTable<T> tab) {
+  __shared__ float2_lut curve_tab[kWaves][32];
+  const int b = blockIdx.x;
+  int lo = 0, hi = tab.n - 1;  // the last image whose first block is <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab.first[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int i = __builtin_amdgcn_readfirstlane(lo);
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int hw = tab.hw[i];
+  const int groups = (hw + PPL - 1) / PPL;
+  const int first_gw = (b - tab.first[i]) * kThreads + (threadIdx.x & ~63);
+  const int stride = (tab.first[i + 1] - tab.first[i]) * kThreads;  // one trip: the image's blocks cover its groups
+  const int32_t* idn = ids + size_t(i) * steps;
+  const float* prn = params + size_t(i) * steps * EXPO_MAX_PARAMS;
+  float2_lut* const lut = curve_tab[threadIdx.x >> 6];
+  if (!ANY_SLOW || ((tab.vec >> i) & 1))
+    chain_fused_image<T, true, IO>(idn, prn, steps, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut);
+  else
+    chain_fused_image<T, false, IO>(idn, prn, steps, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut);
+}
+
 template <typename T>
 static int chain_fused_fwd_t(const int32_t* ids, const float* params, int steps, const void* x, void* y, int n,
                              int h, int w, hipStream_t s) {
@@ -157,6 +238,51 @@ static int chain_fused_fwd_t(const int32_t* ids, const float* params, int steps,
   else
     hipLaunchKernelGGL((chain_fused_fwd_kernel<T, false, IoCached>), grid, block, 0, s, ids, params, steps, (const T*)x, (T*)y, g.hw, g.groups);
   HIP_TRY(hipGetLastError(), "chain_fused_fwd launch");
+  return EXPO_OK;
+}
+
+// arguments validated by the caller; launches of up to kRaggedMaxImages images each, in order, on stream s
+template <typename T>
+static int chain_fused_fwd_ragged_t(const int32_t* ids, const float* params, int steps, const void* const* xs,
+                                    void* const* ys, const int* hs, const int* ws, int n, hipStream_t s) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  // cache policy from the bytes of the whole call (what a single tensor of the same pixels would choose)
+  long bytes = 0;
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kRaggedMaxImages) {
+    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
+    RaggedTable<T> tab = {};
+    tab.n = m;
+    bool any_slow = false;
+    long blocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      tab.x[j] = static_cast<const T*>(xs[i]);
+      tab.y[j] = static_cast<T*>(ys[i]);
+      tab.hw[j] = hw;
+      tab.first[j] = int(blocks);
+      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
+      // as make_geom: whole 12-byte vectors and 4-byte aligned bases
+      const bool vec = hw % VecTraits<T>::PPV == 0 && ((reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(ys[i])) & 3) == 0;
+      if (vec) tab.vec |= uint64_t(1) << j;
+      any_slow = any_slow || !vec;
+    }
+    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    tab.first[m] = int(blocks);
+    const int32_t* idb = ids + size_t(base) * steps;
+    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
+    if (stream && any_slow)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoStream, true>), grid, block, 0, s, idb, prb, steps, tab);
+    else if (stream)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoStream, false>), grid, block, 0, s, idb, prb, steps, tab);
+    else if (any_slow)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoCached, true>), grid, block, 0, s, idb, prb, steps, tab);
+    else
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoCached, false>), grid, block, 0, s, idb, prb, steps, tab);
+    HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged launch");
+  }
   return EXPO_OK;
 }
 
@@ -175,6 +301,23 @@ int expo_chain_fused_fwd(const int32_t* filter_ids, const float* params, int ste
   hipStream_t s = static_cast<hipStream_t>(stream);
   return dtype == EXPO_F16 ? chain_fused_fwd_t<half_t>(filter_ids, params, steps, x, y, n, h, w, s)
                            : chain_fused_fwd_t<float>(filter_ids, params, steps, x, y, n, h, w, s);
+}
+
+int expo_chain_fused_fwd_ragged(const int32_t* filter_ids, const float* params, int steps, const void* const* xs,
+                                void* const* ys, const int* hs, const int* ws, int n, int dtype, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
+  if (n == 0) return EXPO_OK;
+  if (!xs || !ys || !hs || !ws || (steps > 0 && (!filter_ids || !params))) return fail(EXPO_E_BADARG, "null pointer");
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
+    if (!xs[i] || !ys[i]) return fail(EXPO_E_BADARG, "null image pointer");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return dtype == EXPO_F16 ? chain_fused_fwd_ragged_t<half_t>(filter_ids, params, steps, xs, ys, hs, ws, n, s)
+                           : chain_fused_fwd_ragged_t<float>(filter_ids, params, steps, xs, ys, hs, ws, n, s);
 }
 
 }  // extern "C"

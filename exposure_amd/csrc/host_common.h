@@ -44,6 +44,12 @@ inline int env_int(const char* name, int dflt) {
   return x > 0 ? x : dflt;
 }
 
+// cache policy: tensors of at least EXPO_STREAM_MIN_BYTES (default 8 MiB; L2 is 8 x 4 MiB) stream (IoStream, pixel_io.h)
+inline long stream_min_bytes() {
+  static const long v = env_int("EXPO_STREAM_MIN_BYTES", 8 << 20);
+  return v;
+}
+
 // a reducing kernel writes one workspace record per block: bound the records of one image
 constexpr int kMaxReduceBlocksX = 1024;
 enum GeomKind {
@@ -94,9 +100,7 @@ inline Geom make_geom(int n, int h, int w, std::initializer_list<const void*> pt
   if (reduces && bx > kMaxReduceBlocksX) bx = kMaxReduceBlocksX;
   if (bx < 1) bx = 1;
   g.blocks_x = bx;
-  // cache policy: tensors of at least EXPO_STREAM_MIN_BYTES (default 8 MiB; L2 is 8 x 4 MiB) stream
-  static const long stream_min = env_int("EXPO_STREAM_MIN_BYTES", 8 << 20);
-  g.stream = g.vec && long(n) * g.hw * 3L * long(sizeof(T)) >= stream_min;
+  g.stream = g.vec && long(n) * g.hw * 3L * long(sizeof(T)) >= stream_min_bytes();
   return g;
 }
 

@@ -50,6 +50,53 @@ def fused_chain(high_res, filter_ids, params24):
   return out
 
 
+def fused_chain_ragged(images, filter_ids, params24):
+  """``fused_chain`` over a list of images of different sizes in ONE ragged launch (``expo_chain_fused_fwd_ragged``):
+  images: N device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype; row i of filter_ids (N, steps) / params24
+  (N, steps, 24) is image i's sequence.  Returns the N outputs, each shaped like its input."""
+  from . import _cabi
+  xs = [im.contiguous() for im in images]
+  ys = [torch.empty_like(x) for x in xs]
+  _cabi.chain_fused_fwd_ragged(filter_ids.contiguous().to(torch.int32), params24.contiguous().float(), xs, ys)
+  return ys
+
+
+def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False):
+  """The agent loop of ``retouch`` on the (N, 64, 64, 3) proxies: ``steps`` steps (or until every image stopped), the
+  full-resolution tensor ``hi`` filtered at every step when given (the reference's schedule).  Returns low, states,
+  hi, and per step the selected ids, the C-ABI ids and the (N, 24) parameter rows."""
+  cfg = agent.cfg
+  n, dev = low.shape[0], low.device
+  states = torch.zeros((n, cfg.num_state_dim), dtype=torch.float32, device=dev)  # get_initial_states
+  trace, abi_ids, params = [], [], []
+  for i in range(steps):
+    masks = dropout_masks[i] if dropout_masks is not None else None
+    if hi is None:
+      (low, states, _s, _p), dbg, _ = agent((low, z, states), is_train=0, progress=0.0, dropout_masks=masks)
+    else:
+      (low, states, hi), dbg, _ = agent((low, z, states), is_train=0, progress=0.0, high_res=hi,
+                                        dropout_masks=masks)
+    if generic:  # no (N, 24) parameter rows exist for this configuration: record the ids only
+      abi_ids.append(agent.abi_filter_ids[dbg['selected_filter_ids'].clamp_min(0).long()])
+      params.append(torch.zeros((n, 24), dtype=torch.float32, device=dev))
+    else:
+      abi_ids.append(dbg['abi_filter_ids'])
+      params.append(dbg['params24'])
+    trace.append(dbg['selected_filter_ids'].clone())
+    if bool((states[:, STATE_STOPPED_DIM] > 0).all()):
+      break
+  return low, states, hi, trace, abi_ids, params
+
+
+def _trace_result(out, low, states, trace, abi_ids, params, return_trace):
+  if return_trace == 'full':  # the per-step operations (what net.py:825-877 pickles as decisions / operations)
+    return out, low, states, dict(selected=torch.stack(trace, dim=1), abi_filter_ids=torch.stack(abi_ids, dim=1),
+                                  params24=torch.stack(params, dim=1))
+  if return_trace:
+    return out, low, states, torch.stack(trace, dim=1)
+  return out, low, states
+
+
 @torch.no_grad()
 def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trace=False, fused=True):
   """Run the 5-step retouching loop.  ``high_res``: NHWC device tensor (fp16/fp32), linear RGB.
@@ -70,35 +117,59 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   n = high_res.shape[0]
   dev = high_res.device
   low = make_low_res(high_res, cfg.source_img_size)
-  states = torch.zeros((n, cfg.num_state_dim), dtype=torch.float32, device=dev)  # get_initial_states
   if z is None:
     z = torch.rand((n, cfg.z_dim), device=dev)
-  trace, abi_ids, params = [], [], []
   hi = high_res.contiguous()
-  for i in range(steps):
-    masks = dropout_masks[i] if dropout_masks is not None else None
-    if fused:
-      (low, states, _s, _p), dbg, _ = agent((low, z, states), is_train=0, progress=0.0, dropout_masks=masks)
-    else:
-      (low, states, hi), dbg, _ = agent((low, z, states), is_train=0, progress=0.0, high_res=hi,
-                                        dropout_masks=masks)
-    if generic:  # no (N, 24) parameter rows exist for this configuration: record the ids only
-      abi_ids.append(agent.abi_filter_ids[dbg['selected_filter_ids'].clamp_min(0).long()])
-      params.append(torch.zeros((n, 24), dtype=torch.float32, device=dev))
-    else:
-      abi_ids.append(dbg['abi_filter_ids'])
-      params.append(dbg['params24'])
-    trace.append(dbg['selected_filter_ids'].clone())
-    if bool((states[:, STATE_STOPPED_DIM] > 0).all()):
-      break
-  if fused:
-    hi = fused_chain(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1))
-  if return_trace == 'full':  # the per-step operations (what net.py:825-877 pickles as decisions / operations)
-    return hi, low, states, dict(selected=torch.stack(trace, dim=1), abi_filter_ids=torch.stack(abi_ids, dim=1),
-                                 params24=torch.stack(params, dim=1))
-  if return_trace:
-    return hi, low, states, torch.stack(trace, dim=1)
-  return hi, low, states
+  low, states, stepped, trace, abi_ids, params = _agent_steps(agent, low, z, steps, dropout_masks,
+                                                              hi=None if fused else hi, generic=generic)
+  hi = fused_chain(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)) if fused else stepped
+  return _trace_result(hi, low, states, trace, abi_ids, params, return_trace)
+
+
+@torch.no_grad()
+def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False):
+  """``retouch`` over a list of images of ANY sizes at once (the batching ``evaluate.py:18`` asks for, without its
+  same-resolution restriction).  ``images``: N device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype and device.
+  One 64x64 proxy per image (``make_low_res``) is stacked, the agent runs once on the (N, 64, 64, 3) stack, and the
+  recorded sequences are applied to the full-resolution images in ONE ragged launch (``fused_chain_ragged``).  ``z``
+  (N, z_dim) and ``dropout_masks`` (per step, (N, ...) rows) as in ``retouch``.  Stopping is uniform across a batch
+  (``submitted = is_last_step``), so every image runs the same number of steps.
+
+  Returns (list of N outputs shaped like their inputs, low (N, 64, 64, 3), states (N, D)[, trace]) with the trace in
+  ``retouch``'s shapes.  Where ``retouch`` cannot fuse (``cfg.masking``, or ``cfg.curve_steps != 8``: the reference's
+  schedule on the generic kernels) every image goes through ``retouch`` alone, with its rows of ``z`` and masks (z is
+  still drawn once for the batch when not given), and the per-image results are concatenated."""
+  cfg = agent.cfg
+  images = list(images)
+  n = len(images)
+  if n == 0:
+    raise ValueError('retouch_batch: no images')
+  dev = images[0].device
+  for im in images:
+    if im.dtype != images[0].dtype or im.device != dev or im.shape[-1] != 3 or not (
+        im.dim() == 3 or (im.dim() == 4 and im.shape[0] == 1)):
+      raise ValueError('retouch_batch: images must be (H, W, 3) or (1, H, W, 3) tensors of one dtype and device')
+  steps = steps or cfg.test_steps
+  if z is None:
+    z = torch.rand((n, cfg.z_dim), device=dev)
+  hi4 = [im if im.dim() == 4 else im[None] for im in images]
+  generic = any(f.uses_generic_kernels() for f in agent.filters)
+  if cfg.masking or generic:  # no parameters-only replay: per image, the schedule retouch picks for it
+    rows = []
+    for i, im in enumerate(hi4):
+      masks = None if dropout_masks is None else [tuple(m[i:i + 1] for m in step) for step in dropout_masks]
+      rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=masks, return_trace=return_trace or True))
+    outs = [r[0].reshape(im.shape) for r, im in zip(rows, images)]
+    low, states = torch.cat([r[1] for r in rows]), torch.cat([r[2] for r in rows])
+    if return_trace == 'full':
+      return outs, low, states, {k: torch.cat([r[3][k] for r in rows]) for k in rows[0][3]}
+    if return_trace:
+      return outs, low, states, torch.cat([r[3] for r in rows])
+    return outs, low, states
+  low = torch.cat([make_low_res(im, cfg.source_img_size) for im in hi4])
+  low, states, _hi, trace, abi_ids, params = _agent_steps(agent, low, z, steps, dropout_masks)
+  outs = fused_chain_ragged(images, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1))
+  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
 
 
 def load_image(path):
@@ -174,7 +245,8 @@ FILTER_BY_SHORT_NAME = {'E': 'ExposureFilter', 'G': 'GammaFilter', 'W': 'Improve
 def main(argv=None):
   """``python -m exposure_amd.evaluate [--filters E,G] [--weights w.pt | --tf-checkpoint dir] [--out dir|file] img ...`` -- the
   tensor part of ``evaluate.py:8-31`` / ``GAN.eval`` (``net.py:711-821``): per image, load (16-bit TIFF or
-  8-bit sRGB), 5 retouching steps on the GPU, write the linear result.  Returns one record per image."""
+  8-bit sRGB), 5 retouching steps on the GPU, write the linear result.  With ``--batch N`` the images go through
+  ``retouch_batch`` in groups of up to N (same files and records).  Returns one record per image."""
   import argparse
   import numpy as np
   from . import filters as F
@@ -200,6 +272,11 @@ def main(argv=None):
   ap.add_argument('--seed', type=int, default=None, help='seeds the random-init weights / dropout / noise')
   ap.add_argument('--stepwise', action='store_true', help="the reference's schedule: filter the full-resolution "
                   'tensor at every step instead of one fused pass at the end')
+  ap.add_argument('--batch', type=int, default=1, metavar='N',
+                  help='retouch up to N images at once, of any sizes, grouped in argument order (retouch_batch: the '
+                  'agent runs on the stacked proxies, one ragged launch applies the filters).  z and the dropout '
+                  'masks are drawn per batch, so --seed with --batch N does not reproduce --batch 1; with --stepwise '
+                  'every image runs alone')
   args = ap.parse_args(argv)
   dev = torch.device('cuda:0')
   if args.seed is not None:
@@ -217,10 +294,12 @@ def main(argv=None):
     from . import checkpoint
     checkpoint.restore(agent, args.tf_checkpoint, args.ckpt)
   dt = torch.float16 if args.dtype == 'f16' else torch.float32
+  if args.batch < 1:
+    ap.error('--batch must be >= 1')
   records = []
-  for path in args.images:
-    hi = torch.from_numpy(np.ascontiguousarray(load_image(path))).to(dev).to(dt)[None]
-    out, _low, states, ops = retouch(agent, hi, return_trace='full', fused=not args.stepwise)
+
+  def emit(path, hi, out, states, ops):
+    """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows)"""
     trace = ops['selected']
     names = [agent.filters[int(j)].get_short_name() for j in trace[0]]
     print('%s: %dx%d  filters: %s' % (path, hi.shape[2], hi.shape[1], ' '.join(names)))
@@ -236,6 +315,22 @@ def main(argv=None):
     records.append(dict(image=path, output=dst, png=pngs, filters=names, states=states[0].cpu().tolist(),
                         abi_filter_ids=ops['abi_filter_ids'][0].cpu().tolist(),
                         params24=ops['params24'][0].cpu().numpy()))
+
+  def load(path):
+    return torch.from_numpy(np.ascontiguousarray(load_image(path))).to(dev).to(dt)[None]
+
+  if args.batch == 1 or args.stepwise:
+    for path in args.images:
+      hi = load(path)
+      out, _low, states, ops = retouch(agent, hi, return_trace='full', fused=not args.stepwise)
+      emit(path, hi, out, states, ops)
+    return records
+  for b in range(0, len(args.images), args.batch):
+    paths = args.images[b:b + args.batch]
+    his = [load(path) for path in paths]
+    outs, _low, states, ops = retouch_batch(agent, his, return_trace='full')
+    for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
+      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()})
   return records
 
 

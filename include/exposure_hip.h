@@ -48,12 +48,13 @@
 extern "C" {
 #endif
 
-#define EXPO_ABI_VERSION 8 /* 2: caller-owned reduction workspace (no float atomics, no fills); 3: derivatives of the
+#define EXPO_ABI_VERSION 9 /* 2: caller-owned reduction workspace (no float atomics, no fills); 3: derivatives of the
                               critic statistics and of the penalty, VignetFilter, bias + lrelu, masked per-image dispatch;
                               4: Tone / Color curves of any cfg.curve_steps (expo_curve_*); 5: the convnets' convolution
                               (expo_conv4x4s2_*); 6: its mask / bias variants, the hand-scheduled critic update's
                               kernels, expo_build_info; 7: expo_net_inputs, the first FC layer with its K dimension split
-                              (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan */
+                              (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
+                              9: expo_chain_fused_fwd_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -296,6 +297,23 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts,
  */
 int expo_chain_fused_fwd(const int32_t* filter_ids, const float* params, int steps,
                          const void* x, void* y, int n, int h, int w, int dtype, void* stream);
+
+/*
+ * (ABI 9) expo_chain_fused_fwd over a LIST of n images of any sizes, in one launch (several for n > 64: the table of
+ * images travels in the kernel arguments, 64 per launch, all on `stream` in order).  Every output is bit-identical to
+ * expo_chain_fused_fwd on that image alone (same step loop; only cache bits and addressing differ).
+ *   filter_ids  device int32 [n][steps] in [-1, 8], params device float32 [n][steps][EXPO_MAX_PARAMS]: as above
+ *   xs, ys      HOST arrays of n device image pointers (NHWC, 3 channels, `dtype` storage; as the pointer arrays of
+ *               expo_chain_bwd); image i has hs[i] x ws[i] pixels (host arrays).  Outputs must not overlap any image
+ *               of the call but their own input.
+ * Everything is validated before anything is enqueued: every image as expo_chain_fused_fwd's one (h, w >= 1, smaller
+ * than 2 GiB), steps in [0, 64], no null pointer; n == 0 is a no-op.  Per image the dwordx3 path is taken when its
+ * pixel count is whole 12-byte vectors and both bases are 4-byte aligned (else element-wise); the streaming cache
+ * policy when the whole call moves at least EXPO_STREAM_MIN_BYTES.
+ */
+int expo_chain_fused_fwd_ragged(const int32_t* filter_ids, const float* params, int steps,
+                                const void* const* xs, void* const* ys, const int* hs, const int* ws,
+                                int n, int dtype, void* stream);
 
 /*
  * One-pass backward of the same fixed per-image sequence: dx = d(loss)/dx and every step's parameter
