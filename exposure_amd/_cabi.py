@@ -21,6 +21,7 @@ EXPO_ABI_VERSION = 9
 EXPO_CURVE_MAX_STEPS = 16
 EXPO_F16, EXPO_F32 = 0, 1
 EXPO_MAX_PARAMS = 24
+EXPO_TAP_STORAGE, EXPO_TAP_U8 = 0, 1
 NUM_PARAMS = (1, 1, 3, 1, 8, 1, 1, 24, 2)  # ids 0..7 = cfg.filters order, 8 = LevelFilter
 
 # every symbol include/exposure_hip.h declares: name -> (restype, argtypes)
@@ -83,6 +84,10 @@ SIGNATURES = {
     'expo_chain_fused_fwd': (_i, [_vp, _fp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     'expo_chain_fused_fwd_ragged': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i),
                                          ctypes.POINTER(_i), _i, _i, _vp]),
+    'expo_chain_fused_fwd_taps': (_i, [_vp, _fp, _i, _vp, _vp, _i, _i, _i, _i, ctypes.c_uint64, _i, _vp, _vp]),
+    'expo_chain_fused_fwd_ragged_taps': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                              ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
+                                              ctypes.POINTER(_vp), _vp]),
     'expo_chain_fused_bwd': (_i, [_vp, _fp, _i, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_critic_stats': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_overexposure_penalty': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -509,6 +514,111 @@ def chain_fused_fwd_ragged(filter_ids, params, xs, ys):
     _check(lib.expo_chain_fused_fwd_ragged(_ptr(filter_ids), _ptr(params), steps, _ptr_array(xs), _ptr_array(ys),
                                            (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]),
                                            _stream()), 'expo_chain_fused_fwd_ragged')
+
+
+def _tap_format(taps, dt):
+  """EXPO_TAP_U8 for uint8 tap tensors, EXPO_TAP_STORAGE for taps of the images' dtype"""
+  if taps.dtype is torch.uint8:
+    return EXPO_TAP_U8
+  if taps.dtype is dt:
+    return EXPO_TAP_STORAGE
+  raise ExposureHipError('exposure_amd: taps must be uint8 or of the images\' dtype %s, got %s' % (dt, taps.dtype))
+
+
+def _tap_count(tap_mask, steps):
+  tap_mask = int(tap_mask)
+  if tap_mask < 0 or tap_mask >> steps:
+    raise ExposureHipError('exposure_amd: tap_mask 0x%x has a bit outside the %d steps' % (tap_mask, steps))
+  return bin(tap_mask).count('1')
+
+
+def chain_fused_fwd_taps(filter_ids, params, x, y, tap_mask, taps):
+  """``chain_fused_fwd`` that also writes the image after every step k whose bit is set in tap_mask
+  (``expo_chain_fused_fwd_taps``).  taps: (T, N, H, W, 3) contiguous device tensor, T = popcount(tap_mask), tap j the
+  j-th set bit; uint8 -> the 8-bit PNG values (EXPO_TAP_U8), x's dtype -> the storage values (EXPO_TAP_STORAGE).  y may
+  be None (taps only); taps may be None when tap_mask is 0."""
+  lib = load()
+  _img(x, 'x')
+  if y is not None:
+    _img(y, 'y')
+    if y.shape != x.shape or y.dtype != x.dtype or y.device != x.device:
+      raise ExposureHipError('exposure_amd: y must be shaped, typed and placed like x')
+  n, h, w, _ = x.shape
+  steps = filter_ids.shape[1]
+  if not filter_ids.is_cuda or filter_ids.dtype != torch.int32 or not filter_ids.is_contiguous() or \
+      tuple(filter_ids.shape) != (n, steps):
+    raise ExposureHipError('exposure_amd: filter_ids must be a contiguous int32 device tensor of shape (N, steps)')
+  _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
+  t = _tap_count(tap_mask, steps)
+  fmt = EXPO_TAP_STORAGE
+  if taps is not None:
+    fmt = _tap_format(taps, x.dtype)
+    if not taps.is_cuda or taps.device != x.device or not taps.is_contiguous() or tuple(taps.shape) != (t, n, h, w, 3):
+      raise ExposureHipError('exposure_amd: taps must be a contiguous device tensor of shape %s on x\'s device, got %s'
+                             % ((t, n, h, w, 3), tuple(taps.shape)))
+  with torch.cuda.device(x.device):
+    _check(lib.expo_chain_fused_fwd_taps(_ptr(filter_ids), _ptr(params), steps, _ptr(x), _ptr(y), n, h, w,
+                                         _dtype_code(x), tap_mask, fmt, _ptr(taps), _stream()),
+           'expo_chain_fused_fwd_taps')
+
+
+def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
+  """``chain_fused_fwd_ragged`` with taps (``expo_chain_fused_fwd_ragged_taps``): taps is a list of N contiguous device
+  tensors, taps[i] (T, H_i, W_i, 3) of one dtype (uint8 or the images' dtype, as in ``chain_fused_fwd_taps``).  ys may
+  be None (taps only); taps may be None when tap_mask is 0.  The per-image checks are as lean as the call without
+  taps."""
+  lib = load()
+  n = len(xs)
+  if ys is not None and len(ys) != n:
+    raise ExposureHipError('exposure_amd: xs and ys must have the same length')
+  if taps is not None and len(taps) != n:
+    raise ExposureHipError('exposure_amd: xs and taps must have the same length')
+  if filter_ids.dim() != 2 or filter_ids.shape[0] != n or not filter_ids.is_cuda or filter_ids.dtype != torch.int32 or \
+      not filter_ids.is_contiguous():
+    raise ExposureHipError('exposure_amd: filter_ids must be a contiguous int32 device tensor of shape (N, steps)')
+  steps = filter_ids.shape[1]
+  _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
+  t = _tap_count(tap_mask, steps)
+  if n == 0:
+    return
+  dt, dev = xs[0].dtype, filter_ids.get_device()
+  if params.get_device() != dev:
+    raise ExposureHipError('exposure_amd: filter_ids and params must be on the images\' device')
+  fmt, tdt = EXPO_TAP_STORAGE, None
+  if taps is not None:
+    fmt = _tap_format(taps[0], dt)
+    tdt = taps[0].dtype
+  hs, ws = [0] * n, [0] * n
+  for i in range(n):
+    x = xs[i]
+    if not isinstance(x, torch.Tensor):
+      raise ExposureHipError('exposure_amd: xs[%d] must be a tensor' % i)
+    sx = x.shape
+    if sx[-1] != 3 or not (len(sx) == 3 or (len(sx) == 4 and sx[0] == 1)):
+      raise ExposureHipError('exposure_amd: xs[%d] %s must be (H, W, 3) or (1, H, W, 3)' % (i, tuple(sx)))
+    if x.dtype is not dt or x.get_device() != dev or not x.is_contiguous():
+      raise ExposureHipError('exposure_amd: every image must be a contiguous ROCm device tensor of one dtype, on the '
+                             'device of filter_ids (HIP path only, no CPU fallback)')
+    h, w = sx[-3], sx[-2]
+    if ys is not None:
+      y = ys[i]
+      if not isinstance(y, torch.Tensor) or y.shape != sx or y.dtype is not dt or y.get_device() != dev or \
+          not y.is_contiguous():
+        raise ExposureHipError('exposure_amd: ys[%d] must be a contiguous device tensor shaped and typed like xs[%d]'
+                               % (i, i))
+    if taps is not None:
+      tp = taps[i]
+      if not isinstance(tp, torch.Tensor) or tp.shape != (t, h, w, 3) or tp.dtype is not tdt or \
+          tp.get_device() != dev or not tp.is_contiguous():
+        raise ExposureHipError('exposure_amd: taps[%d] must be a contiguous device tensor (%d, %d, %d, 3) of the '
+                               'dtype of taps[0]' % (i, t, h, w))
+    hs[i], ws[i] = h, w
+  with torch.cuda.device(dev):
+    _check(lib.expo_chain_fused_fwd_ragged_taps(_ptr(filter_ids), _ptr(params), steps, _ptr_array(xs),
+                                                None if ys is None else _ptr_array(ys), (ctypes.c_int * n)(*hs),
+                                                (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]), tap_mask, fmt,
+                                                None if taps is None else _ptr_array(taps), _stream()),
+           'expo_chain_fused_fwd_ragged_taps')
 
 
 FUSED_BWD_MAX_STEPS = 8  # EXPO_FUSED_BWD_MAX_STEPS

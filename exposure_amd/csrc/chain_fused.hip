@@ -24,6 +24,9 @@
 #ifndef EXPO_FUSED_MIN_WAVES
 #define EXPO_FUSED_MIN_WAVES  // e.g. -DEXPO_FUSED_MIN_WAVES=,8 : register budget for 8 waves per SIMD (probe builds)
 #endif
+#ifndef EXPO_TAPS_MIN_WAVES
+#define EXPO_TAPS_MIN_WAVES  // the same for the tap kernels (,4 spills the fp16 u8 kernels: 128 VGPRs are too few)
+#endif
 
 namespace expo {
 
@@ -40,9 +43,13 @@ namespace expo {
 // prn[steps][EXPO_MAX_PARAMS] (wave-uniform), `tab` this wave's curve table in LDS, `plane` the parameter this lane
 // mirrors for the curve builds.  Shared by the dense kernel (one (N, H, W, 3) tensor) and the ragged one (a list of
 // images of any sizes).
-template <typename T>
+// `tap(k, out)` sees the image after step k (the tap kernels below); the default does nothing and the kernels without
+// taps compile to the same code as before it existed.
+struct NoTap { __device__ void operator()(int, const float*) const {} };
+template <typename T, class Tap = NoTap>
 __device__ inline void chain_fused_run(const int32_t* idn, const float* prn,
-                                                int steps, float2_lut* tab, int plane, float* v) {
+                                                int steps, float2_lut* tab, int plane, float* v,
+                                                const Tap& tap = Tap()) {
   constexpr int PPL = PixTraits<T>::PPL;
   // One step, OUT OF PLACE (in -> out).  The step loop below runs two steps per trip with the two pixel arrays (and
   // the two parameter sets) swapping roles, so no loop-carried value is ever copied: the rolled one-step loop paid 24
@@ -113,8 +120,10 @@ __device__ inline void chain_fused_run(const int32_t* idn, const float* prn,
   for (int st = 0; st < steps; st += 2) {
     fetch(st + 1, pb, kb, ib);
     apply(ia, pa, ka, a, w);
+    tap(st, w);
     fetch(st + 2, pa, ka, ia);
     apply(ib, pb, kb, w, a);
+    tap(st + 1, a);  // (st + 1 == steps: the identity half-trip, never a tap)
   }
 #pragma unroll
   for (int j = 0; j < PPL * 3; ++j) v[j] = a[j];
@@ -225,6 +234,190 @@ __global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd
     chain_fused_image<T, false, IO>(idn, prn, steps, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut);
 }
 
+// ------------------------------------------------------- taps: the image after chosen steps, from the same pass
+// The step-by-step pictures of net.py:820-823 without reading the image back: after every step k whose bit is set in
+// the (uniform) tap_mask, the running fp32 values of the pixel group are also written to tap plane j = the number of
+// set bits below k.  Separate instantiations: the kernels above keep their code.
+//   EXPO_TAP_STORAGE: pack<T> / store_slow<T>, the very stores of y -- the tap is what the truncated sequence writes.
+//   EXPO_TAP_U8: the value rounded to T first, then saturate(rint(s * 255)).  A plane is 3 B/px and may start at any
+//   byte, so on the vector path a lane's 6 (fp16) / 3 (fp32) bytes per 12-byte input vector do not map onto dwords:
+//   they are staged in a per-wave LDS buffer (the wave's chunk as one contiguous 1536 / 768-byte run) and leave as
+//   coalesced buffer_store_dword; a dword that is not 4-byte aligned or straddles the plane's end goes out as four
+//   bounds-checked buffer_store_byte instead (exact, slower).  The element-wise path stores bytes.
+template <typename T>
+__device__ __forceinline__ float tap_u8_level(float v) {
+  const float s = float(T(v));  // rounded to the storage dtype (saturating like pack<T>; either way -> 255)
+  return __builtin_amdgcn_fmed3f(__builtin_rintf(s * 255.0f), 0.0f, 255.0f);
+}
+
+template <typename T, bool VEC, class IO, int FMT>
+struct TapSink {
+  static constexpr int ES = FMT == EXPO_TAP_U8 ? 1 : int(sizeof(T));  // bytes per channel value of a plane
+  static constexpr int BPR = 3 * VecTraits<T>::PPV;                    // u8 bytes per lane and 12-byte input vector
+  char* base;        // plane 0 of this image
+  size_t stride;     // bytes from plane j to plane j + 1
+  uint64_t mask;
+  int hw;
+  uint8_t* stage;    // this wave's 4 * 64 * BPR bytes of LDS (u8 vector path)
+
+  // store the values v (the group of lane `lane`, starting at wave chunk gw; element-wise path: group g = gw + lane)
+  __device__ __forceinline__ void operator()(int k, int gw, int lane, const float* v) const {
+    if (!((mask >> k) & 1)) return;
+    constexpr int PPL = PixTraits<T>::PPL;
+    const int j = __builtin_popcountll(mask & ((uint64_t(1) << k) - 1));
+    char* const plane = base + size_t(j) * stride;
+    if constexpr (!VEC) {
+      if constexpr (FMT == EXPO_TAP_STORAGE) {
+        store_slow<T>(reinterpret_cast<T*>(plane), gw + lane, hw, v);
+      } else {
+        uint8_t* const p = reinterpret_cast<uint8_t*>(plane);
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+          const int px = (gw + lane) * PPL + q;
+          if (px < hw) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[size_t(px) * 3 + c] = uint8_t(uint32_t(tap_u8_level<T>(v[q * 3 + c])));
+          }
+        }
+      }
+    } else if constexpr (FMT == EXPO_TAP_STORAGE) {
+      store_raw<IO::kStore>(make_image_rsrc(reinterpret_cast<T*>(plane), hw), chunk_byte_offset<T>(gw, lane), pack<T>(v));
+    } else {
+      const int nbytes = hw * 3;
+      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(plane, 0, nbytes, kBufferRsrcFlags);
+      // v holds 4 input vectors (rows of the chunk, 64 * BPR bytes apart in the plane), BPR values each in memory order
+#pragma unroll
+      for (int row = 0; row < 4; ++row) {
+        uint8_t* const dst = stage + row * 64 * BPR + lane * BPR;
+        if constexpr (BPR % 2 == 0) {
+#pragma unroll
+          for (int e = 0; e < BPR; e += 2) {
+            uint32_t u = __builtin_amdgcn_cvt_pk_u8_f32(tap_u8_level<T>(v[row * BPR + e]), 0, 0);
+            u = __builtin_amdgcn_cvt_pk_u8_f32(tap_u8_level<T>(v[row * BPR + e + 1]), 1, u);
+            const uint16_t h = uint16_t(u);
+            __builtin_memcpy(dst + e, &h, 2);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < BPR; ++e) dst[e] = uint8_t(uint32_t(tap_u8_level<T>(v[row * BPR + e])));
+        }
+      }
+      __builtin_amdgcn_wave_barrier();  // one wave: its LDS operations execute in order
+      const bool aligned = (reinterpret_cast<uintptr_t>(plane) & 3) == 0;
+      const int chunk = gw * PPL * 3;  // the chunk's first byte in the plane
+#pragma unroll
+      for (int q = 0; q < BPR; ++q) {  // 4 * 64 * BPR bytes = BPR dwords per lane
+        uint32_t d;
+        __builtin_memcpy(&d, stage + (q * 64 + lane) * 4, 4);
+        const int o = chunk + (q * 64 + lane) * 4;
+        if (aligned && o + 4 <= nbytes) {
+          __builtin_amdgcn_raw_buffer_store_b32(d, r, o, 0, IO::kStore);
+        } else {  // bytes past the plane's end are dropped by the buffer's bounds check
+#pragma unroll
+          for (int b = 0; b < 4; ++b) __builtin_amdgcn_raw_buffer_store_b8(uint8_t(d >> (8 * b)), r, o + b, 0, IO::kStore);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();  // the next tap of this wave rewrites the buffer
+    }
+  }
+};
+
+template <typename T, int FMT>
+struct TapStage {
+  static constexpr int kBytes = FMT == EXPO_TAP_U8 ? 4 * 64 * 3 * VecTraits<T>::PPV : 4;
+};
+
+// chain_fused_image with taps; yi may be NULL (taps only)
+template <typename T, bool VEC, class IO, int FMT>
+__device__ __forceinline__ void chain_fused_image_taps(const int32_t* idn, const float* prn, int steps, const T* xi,
+                                                       T* yi, int hw, int groups, int first_gw, int stride,
+                                                       float2_lut* tab, const TapSink<T, VEC, IO, FMT>& sink) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int lane = threadIdx.x & 63;
+  const int plane = lane % EXPO_MAX_PARAMS;
+  if constexpr (VEC) {
+#if EXPO_FP16_OVFL
+    // the fp16 stores (y and storage taps) saturate as in stream_groups, which sets this only when it stores itself
+    if constexpr (sizeof(T) == 2) __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);
+#endif
+    const T* const ins[1] = {xi};
+    const __amdgpu_buffer_rsrc_t ry = make_image_rsrc(yi, hw);
+    stream_groups<T, 1, false, true, IO>(ins, nullptr, hw, first_gw, stride, [&](float (&v)[1][PPL * 3], int g) {
+      const int gw = g - lane;
+      chain_fused_run<T>(idn, prn, steps, tab, plane, v[0], [&](int k, const float* o) { sink(k, gw, lane, o); });
+      if (yi) store_raw<IO::kStore>(ry, chunk_byte_offset<T>(gw, lane), pack<T>(v[0]));
+    });
+  } else {
+    for (int g0 = first_gw; g0 < groups; g0 += stride) {
+      const int g = g0 + lane;
+      float v[PPL * 3];
+      load_slow<T>(xi, g, hw, v);
+      chain_fused_run<T>(idn, prn, steps, tab, plane, v, [&](int k, const float* o) { sink(k, g0, lane, o); });
+      if (yi) store_slow<T>(yi, g, hw, v);
+    }
+  }
+}
+
+template <typename T, bool VEC, class IO, int FMT>
+__global__ __launch_bounds__(kThreads EXPO_TAPS_MIN_WAVES) void chain_fused_fwd_taps_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ params, int steps, const T* __restrict__ x,
+    T* __restrict__ y, int hw, int groups, uint64_t tap_mask, char* __restrict__ taps, int n_images) {
+  __shared__ float2_lut curve_tab[kWaves][32];
+  __shared__ __attribute__((aligned(4))) uint8_t tap_stage[kWaves][TapStage<T, FMT>::kBytes];
+  using Sink = TapSink<T, VEC, IO, FMT>;
+  const int n = blockIdx.y;
+  const size_t off = size_t(n) * hw * 3;
+  const size_t plane_bytes = size_t(hw) * 3 * Sink::ES;
+  const Sink sink{taps + size_t(n) * plane_bytes, size_t(n_images) * plane_bytes, tap_mask, hw,
+                  tap_stage[threadIdx.x >> 6]};
+  chain_fused_image_taps<T, VEC, IO, FMT>(ids + size_t(n) * steps, params + size_t(n) * steps * EXPO_MAX_PARAMS, steps,
+                                          x + off, y ? y + off : nullptr, hw, groups,
+                                          blockIdx.x * kThreads + (threadIdx.x & ~63), gridDim.x * kThreads,
+                                          curve_tab[threadIdx.x >> 6], sink);
+}
+
+// the ragged table plus one tap buffer per image (512 B more by value; the kernarg block stays under 4 KB)
+template <typename T>
+struct RaggedTapTable {
+  RaggedTable<T> t;
+  char* taps[kRaggedMaxImages];
+};
+
+template <typename T, class IO, bool ANY_SLOW, int FMT>
+__global__ __launch_bounds__(kThreads EXPO_TAPS_MIN_WAVES) void chain_fused_fwd_ragged_taps_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ params, int steps, uint64_t tap_mask,
+    const RaggedTapTable<T> tt) {
+  __shared__ float2_lut curve_tab[kWaves][32];
+  __shared__ __attribute__((aligned(4))) uint8_t tap_stage[kWaves][TapStage<T, FMT>::kBytes];
+  const RaggedTable<T>& tab = tt.t;
+  const int b = blockIdx.x;
+  int lo = 0, hi = tab.n - 1;  // the last image whose first block is <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab.first[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int i = __builtin_amdgcn_readfirstlane(lo);
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int hw = tab.hw[i];
+  const int groups = (hw + PPL - 1) / PPL;
+  const int first_gw = (b - tab.first[i]) * kThreads + (threadIdx.x & ~63);
+  const int stride = (tab.first[i + 1] - tab.first[i]) * kThreads;
+  const int32_t* idn = ids + size_t(i) * steps;
+  const float* prn = params + size_t(i) * steps * EXPO_MAX_PARAMS;
+  float2_lut* const lut = curve_tab[threadIdx.x >> 6];
+  uint8_t* const stage = tap_stage[threadIdx.x >> 6];
+  const size_t plane_bytes = size_t(hw) * 3 * TapSink<T, true, IO, FMT>::ES;
+  if (!ANY_SLOW || ((tab.vec >> i) & 1)) {
+    const TapSink<T, true, IO, FMT> sink{tt.taps[i], plane_bytes, tap_mask, hw, stage};
+    chain_fused_image_taps<T, true, IO, FMT>(idn, prn, steps, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut, sink);
+  } else {
+    const TapSink<T, false, IO, FMT> sink{tt.taps[i], plane_bytes, tap_mask, hw, stage};
+    chain_fused_image_taps<T, false, IO, FMT>(idn, prn, steps, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut,
+                                              sink);
+  }
+}
+
 template <typename T>
 static int chain_fused_fwd_t(const int32_t* ids, const float* params, int steps, const void* x, void* y, int n,
                              int h, int w, hipStream_t s) {
@@ -286,6 +479,85 @@ static int chain_fused_fwd_ragged_t(const int32_t* ids, const float* params, int
   return EXPO_OK;
 }
 
+// arguments validated by the caller; tap_mask != 0
+template <typename T, int FMT>
+static int chain_fused_fwd_taps_t(const int32_t* ids, const float* params, int steps, const void* x, void* y, int n,
+                                  int h, int w, uint64_t tap_mask, void* taps, hipStream_t s) {
+  // a storage tap plane is stored like y (dwordx3): its base joins the alignment test; u8 planes handle any base
+  Geom g = make_geom<T>(n, h, w, {x, y, FMT == EXPO_TAP_STORAGE ? taps : nullptr}, kGeomMap);
+  g.blocks_x = (g.groups + kThreads - 1) / kThreads;
+  const dim3 grid(g.blocks_x, n), block(kThreads);
+  const T* xt = static_cast<const T*>(x);
+  T* yt = static_cast<T*>(y);
+  char* tp = static_cast<char*>(taps);
+  if (g.stream)
+    hipLaunchKernelGGL((chain_fused_fwd_taps_kernel<T, true, IoStream, FMT>), grid, block, 0, s, ids, params, steps, xt, yt, g.hw, g.groups, tap_mask, tp, n);
+  else if (g.vec)
+    hipLaunchKernelGGL((chain_fused_fwd_taps_kernel<T, true, IoCached, FMT>), grid, block, 0, s, ids, params, steps, xt, yt, g.hw, g.groups, tap_mask, tp, n);
+  else
+    hipLaunchKernelGGL((chain_fused_fwd_taps_kernel<T, false, IoCached, FMT>), grid, block, 0, s, ids, params, steps, xt, yt, g.hw, g.groups, tap_mask, tp, n);
+  HIP_TRY(hipGetLastError(), "chain_fused_fwd_taps launch");
+  return EXPO_OK;
+}
+
+// arguments validated by the caller; tap_mask != 0, ys NULL = no image output
+template <typename T, int FMT>
+static int chain_fused_fwd_ragged_taps_t(const int32_t* ids, const float* params, int steps, const void* const* xs,
+                                         void* const* ys, const int* hs, const int* ws, int n, uint64_t tap_mask,
+                                         void* const* taps, hipStream_t s) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  long bytes = 0;
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kRaggedMaxImages) {
+    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
+    RaggedTapTable<T> tt = {};
+    RaggedTable<T>& tab = tt.t;
+    tab.n = m;
+    bool any_slow = false;
+    long blocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      tab.x[j] = static_cast<const T*>(xs[i]);
+      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+      tt.taps[j] = static_cast<char*>(taps[i]);
+      tab.hw[j] = hw;
+      tab.first[j] = int(blocks);
+      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
+      const uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
+                          (FMT == EXPO_TAP_STORAGE ? reinterpret_cast<uintptr_t>(taps[i]) : 0);
+      const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
+      if (vec) tab.vec |= uint64_t(1) << j;
+      any_slow = any_slow || !vec;
+    }
+    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    tab.first[m] = int(blocks);
+    const int32_t* idb = ids + size_t(base) * steps;
+    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
+    if (stream && any_slow)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoStream, true, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
+    else if (stream)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoStream, false, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
+    else if (any_slow)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoCached, true, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
+    else
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoCached, false, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
+    HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged_taps launch");
+  }
+  return EXPO_OK;
+}
+
+// kernel arguments of the ragged tap kernel: ids, params, steps, tap_mask, the table
+static_assert(sizeof(RaggedTapTable<half_t>) + 32 <= 4096, "the ragged tap table must fit the 4 KB kernarg block");
+
+static int check_taps(int steps, uint64_t tap_mask, int tap_format) {
+  if (tap_format != EXPO_TAP_STORAGE && tap_format != EXPO_TAP_U8)
+    return fail(EXPO_E_BADARG, "tap_format must be EXPO_TAP_STORAGE or EXPO_TAP_U8");
+  if (steps < 64 && (tap_mask >> steps) != 0) return fail(EXPO_E_BADARG, "tap_mask has a bit >= steps");
+  return EXPO_OK;
+}
+
 }  // namespace expo
 
 using namespace expo;
@@ -318,6 +590,56 @@ int expo_chain_fused_fwd_ragged(const int32_t* filter_ids, const float* params, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   return dtype == EXPO_F16 ? chain_fused_fwd_ragged_t<half_t>(filter_ids, params, steps, xs, ys, hs, ws, n, s)
                            : chain_fused_fwd_ragged_t<float>(filter_ids, params, steps, xs, ys, hs, ws, n, s);
+}
+
+int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, int steps, const void* x, void* y,
+                              int n, int h, int w, int dtype, uint64_t tap_mask, int tap_format, void* taps,
+                              void* stream) {
+  if (int rc = check_common(n, h, w, dtype)) return rc;
+  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
+  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
+  if (!y && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (y NULL and tap_mask 0)");
+  if (n == 0) return EXPO_OK;
+  if (!x || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params))) return fail(EXPO_E_BADARG, "null pointer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool f16 = dtype == EXPO_F16;
+  if (!tap_mask)
+    return f16 ? chain_fused_fwd_t<half_t>(filter_ids, params, steps, x, y, n, h, w, s)
+               : chain_fused_fwd_t<float>(filter_ids, params, steps, x, y, n, h, w, s);
+  if (tap_format == EXPO_TAP_U8)
+    return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_U8>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
+               : chain_fused_fwd_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
+  return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
+             : chain_fused_fwd_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
+}
+
+int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* params, int steps,
+                                     const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
+                                     int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
+  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
+  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
+  if (n == 0) return EXPO_OK;
+  if (!xs || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
+    return fail(EXPO_E_BADARG, "null pointer");
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
+    if (!xs[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
+    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool f16 = dtype == EXPO_F16;
+  if (!tap_mask)
+    return f16 ? chain_fused_fwd_ragged_t<half_t>(filter_ids, params, steps, xs, ys, hs, ws, n, s)
+               : chain_fused_fwd_ragged_t<float>(filter_ids, params, steps, xs, ys, hs, ws, n, s);
+  if (tap_format == EXPO_TAP_U8)
+    return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
+               : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
+  return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
+             : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
 }
 
 }  // extern "C"

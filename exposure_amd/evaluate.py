@@ -9,7 +9,8 @@ dropout stays on, as in the reference (``agent.py:36``), unless masks are passed
 
 Image decoding (16-bit TIFF / ProPhoto linearisation, ``util.py:311-323, 495-501``) sits in ``load_image``; of the
 outputs of ``net.py:825-877`` the CLI writes the linear result (.npy) and, with ``--png``, the reference's 8-bit
-``retouched`` / ``input_tone_mapped`` pictures; the debug pickle and the cv2-drawn ``steps`` panel are out of scope.
+``retouched`` / ``input_tone_mapped`` pictures; with ``--step-by-step`` also the ``intermediateNN`` pictures of
+``net.py:820-823`` (``evaluate.py:31``); the debug pickle and the cv2-drawn ``steps`` panel are out of scope.
 """
 import numpy as np
 import torch
@@ -61,14 +62,55 @@ def fused_chain_ragged(images, filter_ids, params24):
   return ys
 
 
-def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False):
+def fused_chain_taps(high_res, filter_ids, params24, tap_mask, tap_dtype, out=True):
+  """``fused_chain`` that also returns the image after every step k whose bit is set in ``tap_mask``, from the same
+  pass (``expo_chain_fused_fwd_taps``): (out or None, taps (T, N, H, W, 3) of ``tap_dtype``: torch.uint8 for the 8-bit
+  PNG values, else high_res's dtype)."""
+  from . import _cabi
+  x = high_res.contiguous()
+  y = torch.empty_like(x) if out else None
+  t = bin(tap_mask).count('1')
+  taps = torch.empty((t,) + tuple(x.shape), dtype=tap_dtype, device=x.device)
+  _cabi.chain_fused_fwd_taps(filter_ids.contiguous().to(torch.int32), params24.contiguous().float(), x, y, tap_mask,
+                             taps if t else None)
+  return y, taps
+
+
+def fused_chain_ragged_taps(images, filter_ids, params24, tap_mask, tap_dtype, out=True):
+  """``fused_chain_ragged`` with taps (``expo_chain_fused_fwd_ragged_taps``): (outs or None, per image a (T, H_i, W_i,
+  3) tensor of ``tap_dtype``), one ragged launch per 64 images."""
+  from . import _cabi
+  xs = [im.contiguous() for im in images]
+  ys = [torch.empty_like(x) for x in xs] if out else None
+  t = bin(tap_mask).count('1')
+  taps = [torch.empty((t,) + tuple(x.shape[-3:]), dtype=tap_dtype, device=x.device) for x in xs]
+  _cabi.chain_fused_fwd_ragged_taps(filter_ids.contiguous().to(torch.int32), params24.contiguous().float(), xs, ys,
+                                    tap_mask, taps if t else None)
+  return ys, taps
+
+
+def encode_u8(img):
+  """``save_png``'s 8-bit encoding on the device: saturate(round_half_even(float(img) * 255))."""
+  return torch.round(img.float() * 255.0).clamp_(0, 255).to(torch.uint8)
+
+
+INTERMEDIATES = (None, 'u8', 'storage')
+
+
+def _intermediate_mask(stops):
+  """bit i: step i ran and the image was not stopped after it -- the steps net.py:820-823 saves a picture of"""
+  return sum(1 << i for i, stopped in enumerate(stops) if not stopped)
+
+
+def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, keep_hi=False):
   """The agent loop of ``retouch`` on the (N, 64, 64, 3) proxies: ``steps`` steps (or until every image stopped), the
   full-resolution tensor ``hi`` filtered at every step when given (the reference's schedule).  Returns low, states,
-  hi, and per step the selected ids, the C-ABI ids and the (N, 24) parameter rows."""
+  hi, and per step the selected ids, the C-ABI ids, the (N, 24) parameter rows, whether every image was stopped after
+  it and (``keep_hi``) the full-resolution tensor after it."""
   cfg = agent.cfg
   n, dev = low.shape[0], low.device
   states = torch.zeros((n, cfg.num_state_dim), dtype=torch.float32, device=dev)  # get_initial_states
-  trace, abi_ids, params = [], [], []
+  trace, abi_ids, params, stops, his = [], [], [], [], []
   for i in range(steps):
     masks = dropout_masks[i] if dropout_masks is not None else None
     if hi is None:
@@ -83,9 +125,12 @@ def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False):
       abi_ids.append(dbg['abi_filter_ids'])
       params.append(dbg['params24'])
     trace.append(dbg['selected_filter_ids'].clone())
-    if bool((states[:, STATE_STOPPED_DIM] > 0).all()):
+    if keep_hi:
+      his.append(hi)
+    stops.append(bool((states[:, STATE_STOPPED_DIM] > 0).all()))
+    if stops[-1]:
       break
-  return low, states, hi, trace, abi_ids, params
+  return low, states, hi, trace, abi_ids, params, stops, his
 
 
 def _trace_result(out, low, states, trace, abi_ids, params, return_trace):
@@ -98,9 +143,15 @@ def _trace_result(out, low, states, trace, abi_ids, params, return_trace):
 
 
 @torch.no_grad()
-def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trace=False, fused=True):
+def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trace=False, fused=True,
+            intermediates=None):
   """Run the 5-step retouching loop.  ``high_res``: NHWC device tensor (fp16/fp32), linear RGB.
-  Returns (retouched_high_res, retouched_low_res, states[, trace of selected filter ids]).
+  Returns (retouched_high_res, retouched_low_res, states[, trace of selected filter ids][, intermediates]).
+
+  ``intermediates='u8'`` / ``'storage'`` adds the step-by-step pictures of ``net.py:820-823``: a (S-1, N, H, W, 3)
+  tensor (with the shipped agent every step but the last; in general every step after which the images were not
+  stopped), uint8 ``save_png`` values or the storage dtype.  On the fused path they come from the same pass
+  (``fused_chain_taps``); otherwise they are the per-step tensors, encoded on the device.
 
   ``fused=True`` (default): the agent steps run on the 64x64 proxy only, recording each step's
   (filter id, parameters); the full-resolution image is then read once, pushed through all steps
@@ -108,6 +159,8 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   every step also filters the full-resolution tensor and feeds it back -- identical maths, one
   fp16 rounding per step, ``steps`` times the HBM traffic."""
   cfg = agent.cfg
+  if intermediates not in INTERMEDIATES:
+    raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
   if cfg.masking:
     fused = False  # the spatial mask depends on the running image: no parameters-only replay
   generic = any(f.uses_generic_kernels() for f in agent.filters)
@@ -120,14 +173,29 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   if z is None:
     z = torch.rand((n, cfg.z_dim), device=dev)
   hi = high_res.contiguous()
-  low, states, stepped, trace, abi_ids, params = _agent_steps(agent, low, z, steps, dropout_masks,
-                                                              hi=None if fused else hi, generic=generic)
-  hi = fused_chain(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)) if fused else stepped
-  return _trace_result(hi, low, states, trace, abi_ids, params, return_trace)
+  low, states, stepped, trace, abi_ids, params, stops, his = _agent_steps(
+      agent, low, z, steps, dropout_masks, hi=None if fused else hi, generic=generic,
+      keep_hi=bool(intermediates) and not fused)
+  mask = _intermediate_mask(stops)
+  inter = None
+  if fused and intermediates:
+    hi, inter = fused_chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), mask,
+                                 torch.uint8 if intermediates == 'u8' else hi.dtype)
+  elif fused:
+    hi = fused_chain(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1))
+  else:
+    hi = stepped
+    if intermediates:
+      kept = [h for i, h in enumerate(his) if (mask >> i) & 1]
+      inter = torch.stack(kept) if kept else torch.empty((0,) + tuple(hi.shape), dtype=hi.dtype, device=hi.device)
+      if intermediates == 'u8':
+        inter = encode_u8(inter)
+  res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace)
+  return res + (inter,) if intermediates else res
 
 
 @torch.no_grad()
-def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False):
+def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False, intermediates=None):
   """``retouch`` over a list of images of ANY sizes at once (the batching ``evaluate.py:18`` asks for, without its
   same-resolution restriction).  ``images``: N device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype and device.
   One 64x64 proxy per image (``make_low_res``) is stacked, the agent runs once on the (N, 64, 64, 3) stack, and the
@@ -138,8 +206,13 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
   Returns (list of N outputs shaped like their inputs, low (N, 64, 64, 3), states (N, D)[, trace]) with the trace in
   ``retouch``'s shapes.  Where ``retouch`` cannot fuse (``cfg.masking``, or ``cfg.curve_steps != 8``: the reference's
   schedule on the generic kernels) every image goes through ``retouch`` alone, with its rows of ``z`` and masks (z is
-  still drawn once for the batch when not given), and the per-image results are concatenated."""
+  still drawn once for the batch when not given), and the per-image results are concatenated.
+
+  ``intermediates`` as in ``retouch`` appends a list of N (S-1, H_i, W_i, 3) tensors; on the fused path they come from
+  the ragged launch itself (``fused_chain_ragged_taps``)."""
   cfg = agent.cfg
+  if intermediates not in INTERMEDIATES:
+    raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
   images = list(images)
   n = len(images)
   if n == 0:
@@ -158,18 +231,25 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     rows = []
     for i, im in enumerate(hi4):
       masks = None if dropout_masks is None else [tuple(m[i:i + 1] for m in step) for step in dropout_masks]
-      rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=masks, return_trace=return_trace or True))
+      rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=masks, return_trace=return_trace or True,
+                          intermediates=intermediates))
     outs = [r[0].reshape(im.shape) for r, im in zip(rows, images)]
     low, states = torch.cat([r[1] for r in rows]), torch.cat([r[2] for r in rows])
+    extra = ([r[4][:, 0] for r in rows],) if intermediates else ()
     if return_trace == 'full':
-      return outs, low, states, {k: torch.cat([r[3][k] for r in rows]) for k in rows[0][3]}
+      return (outs, low, states, {k: torch.cat([r[3][k] for r in rows]) for k in rows[0][3]}) + extra
     if return_trace:
-      return outs, low, states, torch.cat([r[3] for r in rows])
-    return outs, low, states
+      return (outs, low, states, torch.cat([r[3] for r in rows])) + extra
+    return (outs, low, states) + extra
   low = torch.cat([make_low_res(im, cfg.source_img_size) for im in hi4])
-  low, states, _hi, trace, abi_ids, params = _agent_steps(agent, low, z, steps, dropout_masks)
-  outs = fused_chain_ragged(images, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1))
-  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks)
+  ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
+  if not intermediates:
+    outs = fused_chain_ragged(images, ids, prm)
+    return _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+  outs, inter = fused_chain_ragged_taps(images, ids, prm, _intermediate_mask(stops),
+                                        torch.uint8 if intermediates == 'u8' else images[0].dtype)
+  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace) + (inter,)
 
 
 def load_image(path):
@@ -214,6 +294,13 @@ def save_png(path, img):
   return path
 
 
+def save_png_u8(path, img_u8):
+  """An (H, W, 3) uint8 array of ``save_png``'s encoding (``encode_u8``, or an EXPO_TAP_U8 tap) written as it is."""
+  from PIL import Image
+  Image.fromarray(np.ascontiguousarray(img_u8), 'RGB').save(path)
+  return path
+
+
 def tone_mapped_input(linear):
   """``net.py:822-823``: max to white, then gamma 1/2.4 -- the ``input_tone_mapped`` picture of ``GAN.eval``."""
   a = np.asarray(linear, dtype=np.float32)
@@ -236,6 +323,8 @@ def output_path(out, image_path, many):
   root, ext = os.path.splitext(out)
   return '%s.%s%s' % (root, os.path.splitext(base)[0], ext or '.npy')
 
+
+CLI_DEVICE = 'cuda:0'  # the device main() runs on (the host tests run the CLI against the CPU stand-in of tests/)
 
 FILTER_BY_SHORT_NAME = {'E': 'ExposureFilter', 'G': 'GammaFilter', 'W': 'ImprovedWhiteBalanceFilter',
                         'S+': 'SaturationPlusFilter', 'T': 'ToneFilter', 'Ct': 'ContrastFilter', 'BW': 'WNBFilter',
@@ -266,6 +355,9 @@ def main(argv=None):
                   help="also write <output>.png (8-bit, the reference's `<name>.retouched.png`, net.py:769-772, 832) "
                   'and, with --show-input, <output>.input_tone_mapped.png (net.py:822-829)')
   ap.add_argument('--show-input', action='store_true')
+  ap.add_argument('--step-by-step', action='store_true',
+                  help="also write <output>.intermediateNN.png, the picture after every step but the last (evaluate.py:31, "
+                  'net.py:820-823); implies --png.  The fused paths write them from the same pass as 8-bit values')
   ap.add_argument('--dtype', default='f16', choices=['f16', 'f32'])
   ap.add_argument('--filters', default=None,
                   help="cfg.filters as comma-separated short names, e.g. 'E,G' (BASELINE config 1); default: all 8")
@@ -278,7 +370,7 @@ def main(argv=None):
                   'masks are drawn per batch, so --seed with --batch N does not reproduce --batch 1; with --stepwise '
                   'every image runs alone')
   args = ap.parse_args(argv)
-  dev = torch.device('cuda:0')
+  dev = torch.device(CLI_DEVICE)
   if args.seed is not None:
     torch.manual_seed(args.seed)
   flt = None
@@ -296,10 +388,14 @@ def main(argv=None):
   dt = torch.float16 if args.dtype == 'f16' else torch.float32
   if args.batch < 1:
     ap.error('--batch must be >= 1')
+  if args.step_by_step:
+    args.png = True
+  inter_kind = 'u8' if args.step_by_step else None
   records = []
 
-  def emit(path, hi, out, states, ops):
-    """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows)"""
+  def emit(path, hi, out, states, ops, inter=None):
+    """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows; inter: its
+    (S-1, H, W, 3) uint8 intermediates with --step-by-step)"""
     trace = ops['selected']
     names = [agent.filters[int(j)].get_short_name() for j in trace[0]]
     print('%s: %dx%d  filters: %s' % (path, hi.shape[2], hi.shape[1], ' '.join(names)))
@@ -312,6 +408,9 @@ def main(argv=None):
       pngs['retouched'] = save_png(stem + '.png', result)
       if args.show_input:
         pngs['input_tone_mapped'] = save_png(stem + '.input_tone_mapped.png', tone_mapped_input(hi[0].float().cpu().numpy()))
+      if inter is not None:
+        for i, a in enumerate(inter.cpu().numpy()):
+          pngs['intermediate%02d' % i] = save_png_u8('%s.intermediate%02d.png' % (stem, i), a)
     records.append(dict(image=path, output=dst, png=pngs, filters=names, states=states[0].cpu().tolist(),
                         abi_filter_ids=ops['abi_filter_ids'][0].cpu().tolist(),
                         params24=ops['params24'][0].cpu().numpy()))
@@ -322,15 +421,16 @@ def main(argv=None):
   if args.batch == 1 or args.stepwise:
     for path in args.images:
       hi = load(path)
-      out, _low, states, ops = retouch(agent, hi, return_trace='full', fused=not args.stepwise)
-      emit(path, hi, out, states, ops)
+      res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind)
+      emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None)
     return records
   for b in range(0, len(args.images), args.batch):
     paths = args.images[b:b + args.batch]
     his = [load(path) for path in paths]
-    outs, _low, states, ops = retouch_batch(agent, his, return_trace='full')
+    res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind)
+    outs, states, ops = res[0], res[2], res[3]
     for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
-      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()})
+      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None)
   return records
 
 

@@ -316,6 +316,33 @@ int expo_chain_fused_fwd_ragged(const int32_t* filter_ids, const float* params, 
                                 int n, int dtype, void* stream);
 
 /*
+ * Taps: expo_chain_fused_fwd / _ragged that also write the running image after chosen steps (the step-by-step
+ * pictures of net.py:820-823, evaluate.py:31), from the same pass -- the image between steps is never read back.
+ * Added exports of ABI 9 (the version is unchanged).
+ *   tap_mask    bit k set: write the image after step k (k < steps).  Tap j is the j-th set bit, T = popcount.
+ *   tap_format  EXPO_TAP_STORAGE: the storage dtype, bit-identical to what expo_chain_fused_fwd writes for the
+ *               truncated sequence filter_ids[:, :k+1].
+ *               EXPO_TAP_U8: uint8 = saturate_[0,255](round_half_even(float(s) * 255.0f)), s the value rounded to the
+ *               storage dtype first: the reference's 8-bit PNG value (cv2.imwrite(img * 255), net.py:769-772).  A NaN
+ *               pixel gives an unspecified byte, as everywhere on the inference path.
+ *   taps        dense: ONE device buffer [T][N][H][W][3], tap-major; ragged: a HOST array of n device buffers,
+ *               image i's [T][hs[i]][ws[i]][3].  A uint8 plane may start at any byte.
+ *   y / ys      may be NULL (only taps are written: the 8-bit preview writes 3 B/px instead of the image's 6 B/px);
+ *               ys may be NULL as a whole array, not per image.
+ * Validated before anything is enqueued: as the calls without taps, plus tap_mask bits < steps, tap_format one of the
+ * two, taps (and every taps[i]) non-NULL when tap_mask != 0, and y / ys NULL with tap_mask == 0 is EXPO_E_BADARG
+ * ("nothing to write").  tap_mask == 0 with y / ys given is exactly the call without taps.
+ */
+#define EXPO_TAP_STORAGE 0
+#define EXPO_TAP_U8 1
+int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, int steps, const void* x, void* y,
+                              int n, int h, int w, int dtype, uint64_t tap_mask, int tap_format, void* taps,
+                              void* stream);
+int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* params, int steps,
+                                     const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
+                                     int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
+
+/*
  * One-pass backward of the same fixed per-image sequence: dx = d(loss)/dx and every step's parameter
  * gradients from x and dy = d(loss)/dy alone -- ONE read of x and dy, ONE write of dx (18 B/pixel
  * whatever the number of steps); the activations are recomputed in registers and no intermediate
