@@ -88,6 +88,9 @@ SIGNATURES = {
     'expo_chain_fused_fwd_ragged_taps': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
                                               ctypes.POINTER(_vp), _vp]),
+    'expo_decode_workspace_bytes': (_sz, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
+    'expo_decode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _fp, _i,
+                                ctypes.POINTER(_vp), _i, _vp, _sz, _vp]),
     'expo_chain_fused_bwd': (_i, [_vp, _fp, _i, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_critic_stats': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_overexposure_penalty': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -619,6 +622,64 @@ def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
                                                 (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]), tap_mask, fmt,
                                                 None if taps is None else _ptr_array(taps), _stream()),
            'expo_chain_fused_fwd_ragged_taps')
+
+
+def decode_workspace_bytes(hs, ws, channels, code_bits):
+  """Bytes of workspace ``decode_ragged`` needs with normalize=1 for images of these sizes (0 for invalid ones)."""
+  n = len(hs)
+  return int(load().expo_decode_workspace_bytes(n, (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), int(channels),
+                                                int(code_bits)))
+
+
+def decode_ragged(codes, table, normalize, outs, workspace=None):
+  """``expo_decode_ragged``: the integer codes of N images to their linear storage tensors, in one ragged call.
+  codes: N contiguous device tensors (H_i, W_i, C), all uint8 or all uint16, one C in {1, 3, 4}; table: contiguous
+  float32 device tensor of 2^bits entries (non-decreasing); outs: N contiguous device tensors (H_i, W_i, 3) or
+  (1, H_i, W_i, 3), float16 or float32, one dtype.  normalize=1 divides by twice the table value of each image's
+  largest code over its output channels (the shared workspace serves it unless ``workspace=`` is given)."""
+  lib = load()
+  n = len(codes)
+  if len(outs) != n:
+    raise ExposureHipError('exposure_amd: codes and outs must have the same length')
+  if n == 0:
+    return
+  ct, dev = codes[0].dtype, table.get_device()
+  bits = {torch.uint8: 8, torch.uint16: 16}.get(ct)
+  if bits is None:
+    raise ExposureHipError('exposure_amd: codes must be uint8 or uint16 tensors, got %s' % ct)
+  if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape) != (1 << bits,):
+    raise ExposureHipError('exposure_amd: table must be a contiguous float32 device tensor of %d entries' % (1 << bits))
+  if codes[0].dim() != 3:
+    raise ExposureHipError('exposure_amd: codes[0] must be (H, W, C), got %s' % (tuple(codes[0].shape),))
+  c, dt = codes[0].shape[2], outs[0].dtype
+  hs, ws = [0] * n, [0] * n
+  for i in range(n):
+    x, y = codes[i], outs[i]
+    if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)):
+      raise ExposureHipError('exposure_amd: codes[%d] / outs[%d] must be tensors' % (i, i))
+    sx, sy = x.shape, y.shape
+    if len(sx) != 3 or sx[2] != c or x.dtype is not ct or x.get_device() != dev or not x.is_contiguous():
+      raise ExposureHipError('exposure_amd: codes[%d] %s must be a contiguous (H, W, %d) %s tensor on the '
+                             'device of the table (HIP path only, no CPU fallback)' % (i, tuple(sx), c, ct))
+    if tuple(sy[-3:]) != (sx[0], sx[1], 3) or not (len(sy) == 3 or (len(sy) == 4 and sy[0] == 1)) or \
+        y.dtype is not dt or y.get_device() != dev or not y.is_contiguous():
+      raise ExposureHipError('exposure_amd: outs[%d] %s must be a contiguous (H, W, 3) or (1, H, W, 3) tensor of one '
+                             'dtype on the table\'s device, H, W = %s' % (i, tuple(sy), tuple(sx[:2])))
+    hs[i], ws[i] = sx[0], sx[1]
+  hsa, wsa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws)
+  with torch.cuda.device(dev):
+    wsp, wsb = ctypes.c_void_p(0), ctypes.c_size_t(0)
+    if normalize:
+      need = int(lib.expo_decode_workspace_bytes(n, hsa, wsa, c, bits))
+      if workspace is None:
+        workspace = reserve_workspace(table.device, need)
+        _order_shared_workspace(table.device)
+      if not workspace.is_cuda or workspace.device != table.device or workspace.numel() * workspace.element_size() < need:
+        raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' %
+                               (need, table.device))
+      wsp, wsb = ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel() * workspace.element_size())
+    _check(lib.expo_decode_ragged(_ptr_array(codes), hsa, wsa, n, c, bits, _ptr(table), int(normalize),
+                                  _ptr_array(outs), _dtype_code(outs[0]), wsp, wsb, _stream()), 'expo_decode_ragged')
 
 
 FUSED_BWD_MAX_STEPS = 8  # EXPO_FUSED_BWD_MAX_STEPS

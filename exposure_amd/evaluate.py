@@ -12,6 +12,8 @@ outputs of ``net.py:825-877`` the CLI writes the linear result (.npy) and, with 
 ``retouched`` / ``input_tone_mapped`` pictures; with ``--step-by-step`` also the ``intermediateNN`` pictures of
 ``net.py:820-823`` (``evaluate.py:31``); the debug pickle and the cv2-drawn ``steps`` panel are out of scope.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -273,6 +275,70 @@ def load_image(path):
   return img / (2 * img.max())  # mimic RAW exposure
 
 
+DECODE_KINDS = ('srgb8', 'srgb16', 'prophoto16')
+DECODE_NORMALIZE = {'srgb8': 1, 'srgb16': 1, 'prophoto16': 0}  # load_image scales the sRGB kinds by 1 / (2 max)
+
+
+def load_raw(path):
+  """``load_image``'s file-level choices without its float maths: (codes (H, W, C) uint8 / uint16 as the file holds
+  them, kind).  ``.tif`` -> the 16-bit samples, 'prophoto16'; a PIL uint16 array -> 'srgb16' (2-D: C = 1); anything
+  else -> ``pil.convert('RGB')``, 'srgb8'.  ``decode_images`` turns them into what ``load_image`` returns."""
+  if path.lower().endswith(('.tif', '.tiff')):
+    from .tiff16 import read_tiff
+    raw = read_tiff(path)
+    if raw.dtype != np.uint16:
+      raise ValueError('expected a 16-bit TIFF')
+    return raw, 'prophoto16'
+  from PIL import Image
+  pil = Image.open(path)
+  raw = np.asarray(pil)
+  if raw.dtype == np.uint16:
+    return (raw[:, :, None] if raw.ndim == 2 else raw), 'srgb16'
+  return np.asarray(pil.convert('RGB')), 'srgb8'
+
+
+_DECODE_TABLES = {}
+
+
+def decode_table(kind, device):
+  """The float32 linearisation of every code of ``kind``: ``load_image``'s own expression evaluated on the code range
+  (cached per kind and device)."""
+  key = (kind, torch.device(device))
+  t = _DECODE_TABLES.get(key)
+  if t is None:
+    if kind == 'srgb8':
+      a = (np.arange(256, dtype=np.float32) / 255.0)**2.2
+    elif kind == 'srgb16':
+      a = (np.arange(65536, dtype=np.float32) / 65535.0)**2.2
+    elif kind == 'prophoto16':
+      a = linearize_ProPhotoRGB(np.arange(65536, dtype=np.float32) / 65535.0)
+    else:
+      raise ValueError('decode kind must be one of %s, got %r' % (DECODE_KINDS, kind))
+    t = _DECODE_TABLES[key] = torch.from_numpy(a).to(key[1])
+  return t
+
+
+def decode_images(raws, dtype, device):
+  """``load_image`` + ``.to(dtype)`` on the device from ``load_raw`` results: the codes are uploaded as they are and
+  ``_cabi.decode_ragged`` makes the linear storage tensors, bit for bit what the host path gives.  One ragged call
+  per distinct (kind, channels); returns (1, H, W, 3) tensors in the order of ``raws``."""
+  from . import _cabi
+  dev = torch.device(device)
+  outs = [None] * len(raws)
+  groups = {}
+  for i, (codes, kind) in enumerate(raws):
+    groups.setdefault((kind, codes.shape[2]), []).append(i)
+  for (kind, _c), idx in groups.items():
+    with warnings.catch_warnings():  # PIL's arrays are read-only: they are only read, by the upload
+      warnings.simplefilter('ignore', UserWarning)
+      cs = [torch.from_numpy(np.ascontiguousarray(raws[i][0])).to(dev) for i in idx]
+    ys = [torch.empty((1, c.shape[0], c.shape[1], 3), dtype=dtype, device=dev) for c in cs]
+    _cabi.decode_ragged(cs, decode_table(kind, dev), DECODE_NORMALIZE[kind], ys)
+    for i, y in zip(idx, ys):
+      outs[i] = y
+  return outs
+
+
 def load_agent_weights(agent, state):
   """Accepts an ``Agent`` state dict, a ``GAN.state_dict()`` (keys prefixed 'generator.' / 'critic.' / 'value.') or the
   ``{'model': GAN.state_dict(), 'optim': ...}`` file that ``python -m exposure_amd.train --save`` writes: the
@@ -369,6 +435,9 @@ def main(argv=None):
                   'agent runs on the stacked proxies, one ragged launch applies the filters).  z and the dropout '
                   'masks are drawn per batch, so --seed with --batch N does not reproduce --batch 1; with --stepwise '
                   'every image runs alone')
+  ap.add_argument('--device-decode', action='store_true',
+                  help='read the images as integer codes (load_raw) and linearise them on the GPU, one ragged call per '
+                  'group of --batch images (decode_images): the same tensors as the default host decode')
   args = ap.parse_args(argv)
   dev = torch.device(CLI_DEVICE)
   if args.seed is not None:
@@ -418,15 +487,20 @@ def main(argv=None):
   def load(path):
     return torch.from_numpy(np.ascontiguousarray(load_image(path))).to(dev).to(dt)[None]
 
+  def load_group(paths):
+    if args.device_decode:
+      return decode_images([load_raw(path) for path in paths], dt, dev)
+    return [load(path) for path in paths]
+
   if args.batch == 1 or args.stepwise:
     for path in args.images:
-      hi = load(path)
+      hi, = load_group([path])
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind)
       emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None)
     return records
   for b in range(0, len(args.images), args.batch):
     paths = args.images[b:b + args.batch]
-    his = [load(path) for path in paths]
+    his = load_group(paths)
     res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind)
     outs, states, ops = res[0], res[2], res[3]
     for i, (path, hi, out) in enumerate(zip(paths, his, outs)):

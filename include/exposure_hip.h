@@ -54,7 +54,7 @@ extern "C" {
                               (expo_conv4x4s2_*); 6: its mask / bias variants, the hand-scheduled critic update's
                               kernels, expo_build_info; 7: expo_net_inputs, the first FC layer with its K dimension split
                               (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
-                              9: expo_chain_fused_fwd_ragged */
+                              9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -341,6 +341,32 @@ int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, in
 int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* params, int steps,
                                      const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                      int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
+
+/*
+ * Decode: the integer codes of n input images, as the file holds them, to the linear storage tensors that
+ * evaluate.load_image + .to(dtype) gives (net.py:726-747).  Added exports of ABI 9 (the version is unchanged).
+ *   codes      HOST array of n device pointers; image i is hs[i] x ws[i] x channels codes, uint8 (code_bits 8) or
+ *              uint16 (16), NHWC.  channels 1, 3 or 4; a pointer may start at any byte (uint8) / element (uint16).
+ *   table      device float32 [2^code_bits], non-decreasing (the caller's contract): the linearisation of every code.
+ *   outs       HOST array of n device pointers, image i's [hs[i]][ws[i]][3] in `dtype`.  With k the code of output
+ *              channel c (channel 0 when channels == 1, channel c otherwise: the alpha channel is ignored):
+ *                normalize 0:  out = cast(table[k])
+ *                normalize 1:  out = cast(fl32(table[k] / fl32(2 table[m_i]))), m_i the largest code of image i over
+ *                              the channels that reach the output; an image of all-zero codes gives NaN everywhere.
+ *              cast rounds to nearest even; the division is the IEEE float32 one.
+ *   workspace  normalize 1 only: caller-owned, 4-byte aligned device scratch of at least expo_decode_workspace_bytes
+ *              (n, hs, ws, channels, code_bits) bytes, no initialisation, nothing carried between calls (one record of
+ *              the largest code per block, then a finish launch writes every image's normalised table into it).
+ *              Ignored with normalize 0.
+ * Three launches per 64 images with normalize 1, one without; larger n is split into launches of 64 on `stream`.
+ * Everything is validated before anything is enqueued (EXPO_E_BADARG / EXPO_E_BADDTYPE): no null pointer, channels,
+ * code_bits and normalize in range, h, w >= 1, an output and the codes of one image smaller than 2 GiB, the
+ * workspace; n == 0 is a no-op.  expo_decode_workspace_bytes is 0 for invalid arguments.
+ */
+size_t expo_decode_workspace_bytes(int n, const int* hs, const int* ws, int channels, int code_bits);
+int expo_decode_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
+                       const float* table, int normalize, void* const* outs, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /*
  * One-pass backward of the same fixed per-image sequence: dx = d(loss)/dx and every step's parameter
