@@ -91,6 +91,9 @@ SIGNATURES = {
     'expo_decode_workspace_bytes': (_sz, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
     'expo_decode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _fp, _i,
                                 ctypes.POINTER(_vp), _i, _vp, _sz, _vp]),
+    'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
+                                     ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
+    'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     'expo_chain_fused_bwd': (_i, [_vp, _fp, _i, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_critic_stats': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_overexposure_penalty': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -680,6 +683,56 @@ def decode_ragged(codes, table, normalize, outs, workspace=None):
       wsp, wsb = ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel() * workspace.element_size())
     _check(lib.expo_decode_ragged(_ptr_array(codes), hsa, wsa, n, c, bits, _ptr(table), int(normalize),
                                   _ptr_array(outs), _dtype_code(outs[0]), wsp, wsb, _stream()), 'expo_decode_ragged')
+
+
+def area_resize_ragged(xs, windows, S, out):
+  """``expo_area_resize_ragged``: INTER_AREA of square windows of linear images, in one ragged call.
+  xs: N contiguous device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype (float16 / float32); windows: Q records
+  (image, y0, x0, side) (any int sequence / array of shape (Q, 4)); out: contiguous device tensor (Q, S, S, 3),
+  float16 or float32, on the images' device."""
+  import numpy as np
+  lib = load()
+  rec = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 4))
+  q, n = rec.shape[0], len(xs)
+  _img(out, 'out')
+  if tuple(out.shape) != (q, S, S, 3):
+    raise ExposureHipError('exposure_amd: out must be (%d, %d, %d, 3), got %s' % (q, S, S, tuple(out.shape)))
+  if q == 0:
+    return out
+  hs, ws = [0] * n, [0] * n
+  for i, x in enumerate(xs):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != out.device or not x.is_contiguous() or \
+        x.shape[-1] != 3 or not (x.dim() == 3 or (x.dim() == 4 and x.shape[0] == 1)) or x.dtype != xs[0].dtype:
+      raise ExposureHipError('exposure_amd: xs[%d] must be a contiguous (H, W, 3) or (1, H, W, 3) tensor of one dtype on '
+                             'the device of out (HIP path only, no CPU fallback)' % i)
+    hs[i], ws[i] = x.shape[-3], x.shape[-2]
+  with torch.cuda.device(out.device):
+    _check(lib.expo_area_resize_ragged(_ptr_array(xs) if n else None, (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n,
+                                       _dtype_code(xs[0]) if n else EXPO_F32,
+                                       rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), q, int(S), _ptr(out),
+                                       _dtype_code(out), _stream()), 'expo_area_resize_ragged')
+  return out
+
+
+def pack_recut(master, records, out):
+  """``expo_pack_recut``: out[r] = flip_r(master[src_r][oy_r:oy_r + C, ox_r:ox_r + C]).  master (M, S, S, 3), out
+  (count, C, C, 3): contiguous device tensors of one dtype; records: contiguous device int32 tensor (count, 4) of
+  (src, oy, ox, flip)."""
+  lib = load()
+  _img(master, 'master')
+  _img(out, 'out')
+  count, c = out.shape[0], out.shape[1]
+  if master.shape[1] != master.shape[2] or out.shape[1] != out.shape[2] or out.dtype != master.dtype or \
+      out.device != master.device:
+    raise ExposureHipError('exposure_amd: master (M, S, S, 3) and out (count, C, C, 3) must be square, of one dtype and '
+                           'on one device, got %s %s / %s %s' % (tuple(master.shape), master.dtype, tuple(out.shape), out.dtype))
+  if not records.is_cuda or records.device != master.device or records.dtype != torch.int32 or \
+      not records.is_contiguous() or tuple(records.shape) != (count, 4):
+    raise ExposureHipError('exposure_amd: records must be a contiguous int32 device tensor of shape (%d, 4)' % count)
+  with torch.cuda.device(master.device):
+    _check(lib.expo_pack_recut(_ptr(master), master.shape[0], master.shape[1], _ptr(records), count, c, _ptr(out),
+                               _dtype_code(out), _stream()), 'expo_pack_recut')
+  return out
 
 
 FUSED_BWD_MAX_STEPS = 8  # EXPO_FUSED_BWD_MAX_STEPS

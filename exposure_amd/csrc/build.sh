@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Eight translation units (decode.hip: the integer codes of an input image to the linear storage tensor, default flags
+# Nine translation units (datasets.hip: the training sets' INTER_AREA master pack and its per-epoch re-cut, default
+# flags; decode.hip: the integer codes of an input image to the linear storage tensor, default flags
 # -- its normalising division must stay IEEE; critic_step.hip: the reductions of the hand-scheduled critic update; conv_ops.hip: the convnets' 4x4 / stride-2 convolution on the f32 matrix cores; curve_generic.hip: Tone / Color for cfg.curve_steps other than 8): the streaming kernels (default flags), the VALU-bound fused inference kernel
 # (-fno-slp-vectorize -fno-honor-nans, see chain_fused.hip), the convnets' activation (nn_ops.hip) and the one-pass
 # backward of a fixed sequence (chain_fused_bwd.hip; -fno-slp-vectorize: the packed-fp32 pairs cost it ~100 VGPRs); extra
@@ -30,6 +31,8 @@ p6=$!
 p7=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/decode.hip" -o "$TMP/decode.o" &
 p8=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/datasets.hip" -o "$TMP/datasets.o" &
+p9=$!
 # (a bare `wait` returns 0 whatever the jobs did: wait for each PID so a failed compile stops the script here)
 wait $p1
 wait $p2
@@ -39,5 +42,6 @@ wait $p5
 wait $p6
 wait $p7
 wait $p8
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" -o "$OUT"
+wait $p9
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -427,12 +427,17 @@ class ReplayMemory:
     (``GAN.train_iteration``): nothing the host decides depends on what the device computes.  The pool's host state
     (order, free slots, mirrors) is advanced here; the device writes happen inside the graph.  -> :class:`IterationPlan`,
     or None (nothing consumed) when the iteration needs the step-by-step path: providers that are not resident in HBM,
-    a pop that would need a refill in the middle, buffers that would have to grow."""
+    a pop that would need a refill in the middle, buffers that would have to grow, a ``PackProvider`` whose epoch is
+    shorter than what one plan may take from it (the refill's whole batches / the real rows)."""
     fd, rd = self.fake_dataset, self.real_dataset
     if not (isinstance(fd, ResidentProvider) and isinstance(rd, ResidentProvider)) or self._img is None:
       return None
     pool_batch = int(self.cfg.batch_size)
     if fd.images.dtype != self._img.dtype or max(batch_size, pool_batch) > min(fd.count, rd.count):
+      return None
+    from .datasets import PackProvider  # (a re-cut at an epoch wrap rewrites the idle half: one wrap per plan at most)
+    if (isinstance(fd, PackProvider) and fd.count < -(-self.target_pool_size // pool_batch) * pool_batch) or \
+        (isinstance(rd, PackProvider) and rd.count < (1 + citers) * batch_size):
       return None
     if self._cap < self.target_pool_size + batch_size or len(self) != self.target_pool_size:
       return None

@@ -1,8 +1,9 @@
 """``python -m exposure_amd.train [--iters N]`` -- the tensor part of the reference's
 ``train.py:9-14`` / ``GAN.train`` (``net.py:298-403``) on synthetic FiveK-shaped data: the G/V and
 critic alternation with the device-resident replay memory, one hipGraph replay per optimisation
-step.  Dataset loading, TensorBoard, PNG dashboards and checkpoints of the reference are out of scope
-(SURVEY.md section 2); ``--save`` writes weights + optimiser state with ``torch.save`` (``--resume`` reads it), ``--save-tf`` a TF-1 checkpoint
+step.  ``--fake-dir`` / ``--real-dir`` train on folders of photos instead (``datasets.py``: the reference's FiveK and
+folder recipes, master packs built on the device, re-cut every epoch; ``--pack-cache`` keeps the packs).  TensorBoard,
+PNG dashboards and checkpoints of the reference are out of scope; ``--save`` writes weights + optimiser state with ``torch.save`` (``--resume`` reads it), ``--save-tf`` a TF-1 checkpoint
 (``checkpoint.py``, ``tf_bundle.py``).
 
 Note on the numbers it prints: with random-init weights the policy can chain Exposure (x11) and
@@ -12,6 +13,7 @@ reference's arithmetic (``filters.py:181-182, 205-206`` have no clamp; ``cfg.cla
 a kernel artefact; ``--clamp`` turns on the reference's own ``clip_by_value(net, 0, 5)``
 (``agent.py:240-241``)."""
 import argparse
+import os
 import time
 
 import torch
@@ -21,7 +23,7 @@ from .gan import GAN
 from .replay_memory import ReplayMemory, ResidentProvider
 
 
-def main(argv=None):
+def parse_args(argv=None):
   ap = argparse.ArgumentParser()
   ap.add_argument('--iters', type=int, default=20, help='training iterations to run (the reference runs 20000)')
   ap.add_argument('--seed', type=int, default=0)
@@ -35,17 +37,67 @@ def main(argv=None):
                   "layouts as the reference's graph declares them (net.py:380-384)")
   ap.add_argument('--clamp', action='store_true', help='cfg.clamp = True (agent.py:240-241)')
   ap.add_argument('--dtype', default='f32', choices=['f32', 'f16'], help='storage type of the image pool')
+  ap.add_argument('--fake-dir', default=None, help='folder of input photos (with --real-dir; default: synthetic data)')
+  ap.add_argument('--real-dir', default=None, help='folder of target photos (with --fake-dir)')
+  ap.add_argument('--fake-recipe', default='fivek', choices=['fivek', 'folder'], help='preprocessing of --fake-dir')
+  ap.add_argument('--real-recipe', default='folder', choices=['fivek', 'folder'], help='preprocessing of --real-dir')
+  ap.add_argument('--fake-list', default=None, help='fold file selecting --fake-dir files (1-based indices)')
+  ap.add_argument('--real-list', default=None, help='fold file selecting --real-dir files (1-based indices)')
+  ap.add_argument('--read-limit', type=int, default=-1, help='read at most this many files of each folder')
+  ap.add_argument('--pack-cache', default=None, metavar='DIR', help='keep the built packs under DIR/fake and DIR/real')
   args = ap.parse_args(argv)
+  if (args.fake_dir is None) != (args.real_dir is None):
+    ap.error('--fake-dir and --real-dir go together')
+  if args.fake_dir is None:
+    for flag in ('fake_list', 'real_list', 'pack_cache'):
+      if getattr(args, flag) is not None:
+        ap.error('--%s needs --fake-dir and --real-dir' % flag.replace('_', '-'))
+    if args.read_limit != -1:
+      ap.error('--read-limit needs --fake-dir and --real-dir')
+  for d in (args.fake_dir, args.real_dir):
+    if d is not None and not os.path.isdir(d):
+      ap.error('%s is not a directory' % d)
+  for f in (args.fake_list, args.real_list):
+    if f is not None and not os.path.isfile(f):
+      ap.error('%s is not a file' % f)
+  return args
+
+
+def photo_providers(args, cfg, dev, dt):
+  """The two PackProviders of --fake-dir / --real-dir (packs from --pack-cache when they match)."""
+  from .datasets import PackProvider, cached_pack
+  provs = []
+  for role, k in (('fake', 1), ('real', 2)):
+    folder, recipe, fold = getattr(args, role + '_dir'), getattr(args, role + '_recipe'), getattr(args, role + '_list')
+    cache = os.path.join(args.pack_cache, role) if args.pack_cache else None
+    t0 = time.time()
+    master, hit = cached_pack(folder, recipe, dt, dev, args.seed + k, fold=fold, read_limit=args.read_limit, cache=cache)
+    print('%s pack: %d rows of %d x %d from %s (%s recipe, %s, %.1f s)' %
+          (role, master.shape[0], master.shape[1], master.shape[2], folder, recipe,
+           'cache hit' if hit else 'built', time.time() - t0))
+    if master.shape[0] < cfg.batch_size:
+      raise SystemExit('%s pack has %d rows, fewer than one batch (%d): add photos' %
+                       (role, master.shape[0], cfg.batch_size))
+    provs.append(PackProvider(master, crop_size=64, seed=args.seed + k))
+  return provs
+
+
+def main(argv=None):
+  args = parse_args(argv)
   dev = torch.device('cuda:0')
   torch.manual_seed(args.seed)
   cfg = make_cfg()
   cfg.clamp = bool(args.clamp)
   gan = GAN(cfg, device=dev, use_graphs=not args.no_graphs, seed=args.seed)  # (--seed also drives dropout / alpha)
   dt = torch.float32 if args.dtype == 'f32' else torch.float16
-  # toy task with the statistics of the real one: dark linear-RAW-like inputs, brighter targets
-  # (both synthetic data sets resident in HBM: 4 096 images each, served as views)
-  memory = ReplayMemory(cfg, ResidentProvider(dev, gamma=2.2, scale=0.35, dtype=dt, seed=args.seed + 1),
-                        ResidentProvider(dev, gamma=1.2, scale=0.9, dtype=dt, seed=args.seed + 2), seed=args.seed)
+  if args.fake_dir is not None:
+    fake, real = photo_providers(args, cfg, dev, dt)
+  else:
+    # toy task with the statistics of the real one: dark linear-RAW-like inputs, brighter targets
+    # (both synthetic data sets resident in HBM: 4 096 images each, served as views)
+    fake = ResidentProvider(dev, gamma=2.2, scale=0.35, dtype=dt, seed=args.seed + 1)
+    real = ResidentProvider(dev, gamma=1.2, scale=0.9, dtype=dt, seed=args.seed + 2)
+  memory = ReplayMemory(cfg, fake, real, seed=args.seed)
   if args.resume:
     ckpt = torch.load(args.resume, map_location=dev)
     gan.load_state_dict(ckpt['model'] if 'model' in ckpt else ckpt)
@@ -62,6 +114,7 @@ def main(argv=None):
   if args.save_tf:
     from . import checkpoint
     print('wrote', checkpoint.save(gan, args.save_tf, args.iters))
+  return hist
 
 
 if __name__ == '__main__':

@@ -54,7 +54,8 @@ extern "C" {
                               (expo_conv4x4s2_*); 6: its mask / bias variants, the hand-scheduled critic update's
                               kernels, expo_build_info; 7: expo_net_inputs, the first FC layer with its K dimension split
                               (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
-                              9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged */
+                              9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged,
+                              expo_area_resize_ragged, expo_pack_recut */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -367,6 +368,33 @@ size_t expo_decode_workspace_bytes(int n, const int* hs, const int* ws, int chan
 int expo_decode_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
                        const float* table, int normalize, void* const* outs, int dtype, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/*
+ * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of
+ * ABI 9 (the version is unchanged).
+ *
+ * expo_area_resize_ragged: q square windows of n linear NHWC images, each resampled to S x S x 3 with OpenCV's
+ * INTER_AREA weights (computeResizeAreaTab, per axis, scale = side / S in double; the 2-D weight is the product).
+ *   xs         HOST array of n device pointers, image i is [hs[i]][ws[i]][3] in in_dtype (EXPO_F16 / EXPO_F32).
+ *   windows    HOST int32 array [q][4]: (image, y0, x0, side); the window is rows y0 .. y0 + side - 1 and columns
+ *              x0 .. x0 + side - 1 of its image.
+ *   out        device [q][S][S][3] in out_dtype, window k at out[k]; cast from the double sum through float32 with
+ *              round-to-nearest-even (fp16 = the fp32 result rounded once more).
+ * Every sum runs in a fixed order (no atomics): a window's result is bit-identical run to run and whatever else the
+ * call holds.  side == S is the identity; side < S (upscaling) is refused.  64 windows per launch, more as further
+ * launches on `stream`.  Validated before anything is enqueued (EXPO_E_BADARG / EXPO_E_BADDTYPE): n, q >= 0, dtypes,
+ * no null pointer, h, w >= 1 and one image < 2 GiB, every window inside its image with side >= S and side / S small
+ * enough for one LDS tile (side <= 4094 S); q == 0 is a no-op.
+ *
+ * expo_pack_recut: out[r] = flip_r(master[src_r][oy_r : oy_r + C, ox_r : ox_r + C]) for r < count, a copy in one
+ * dtype.  master device [m][S][S][3]; records DEVICE int32 [count][4] = (src, oy, ox, flip != 0); out device
+ * [count][C][C][3].  S, C (1 <= C <= S), count, the dtype and the pointers are validated on the host; records out of
+ * range are the caller's contract (clamped on the device, so no read leaves the master).  count == 0 is a no-op.
+ */
+int expo_area_resize_ragged(const void* const* xs, const int* hs, const int* ws, int n, int in_dtype,
+                            const int32_t* windows, int q, int S, void* out, int out_dtype, void* stream);
+int expo_pack_recut(const void* master, int m, int S, const int32_t* records, int count, int C, void* out, int dtype,
+                    void* stream);
 
 /*
  * One-pass backward of the same fixed per-image sequence: dx = d(loss)/dx and every step's parameter
