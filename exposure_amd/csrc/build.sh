@@ -1,11 +1,19 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Nine translation units (datasets.hip: the training sets' INTER_AREA master pack and its per-epoch re-cut, default
-# flags; decode.hip: the integer codes of an input image to the linear storage tensor, default flags
-# -- its normalising division must stay IEEE; critic_step.hip: the reductions of the hand-scheduled critic update; conv_ops.hip: the convnets' 4x4 / stride-2 convolution on the f32 matrix cores; curve_generic.hip: Tone / Color for cfg.curve_steps other than 8): the streaming kernels (default flags), the VALU-bound fused inference kernel
-# (-fno-slp-vectorize -fno-honor-nans, see chain_fused.hip), the convnets' activation (nn_ops.hip) and the one-pass
-# backward of a fixed sequence (chain_fused_bwd.hip; -fno-slp-vectorize: the packed-fp32 pairs cost it ~100 VGPRs); extra
-# arguments go to every compile step.
+# Ten translation units; extra arguments go to every compile step.
+#   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
+#   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
+#                        must reproduce the per-step kernels bit for bit)
+#   chain_fused.hip      the VALU-bound fused inference kernel (-fno-slp-vectorize -fno-honor-nans, see the file)
+#   chain_fused_bwd.hip  the one-pass backward of a fixed sequence (-fno-slp-vectorize: the packed-fp32 pairs cost it
+#                        ~100 VGPRs)
+#   nn_ops.hip           the convnets' activation and glue
+#   curve_generic.hip    Tone / Color for cfg.curve_steps other than 8
+#   conv_ops.hip         the convnets' 4x4 / stride-2 convolution on the f32 matrix cores
+#   critic_step.hip      the reductions of the hand-scheduled critic update
+#   decode.hip           the integer codes of an input image to the linear storage tensor (default flags: its
+#                        normalising division must stay IEEE)
+#   datasets.hip         the training sets' INTER_AREA master pack and its per-epoch re-cut (default flags)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -33,6 +41,8 @@ p7=$!
 p8=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/datasets.hip" -o "$TMP/datasets.o" &
 p9=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps.hip" -o "$TMP/chain_steps.o" &
+p10=$!
 # (a bare `wait` returns 0 whatever the jobs did: wait for each PID so a failed compile stops the script here)
 wait $p1
 wait $p2
@@ -43,5 +53,6 @@ wait $p6
 wait $p7
 wait $p8
 wait $p9
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" -o "$OUT"
+wait $p10
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

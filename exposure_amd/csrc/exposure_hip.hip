@@ -2105,6 +2105,18 @@ static ChainPlan chain_plan(int n, int h, int w, int dtype) {
   return plan;
 }
 
+// How many consecutive forward steps of a chunk go into one launch (chain_steps.hip: the group of pixels stays in
+// registers, every intermediate activation is still stored, the re-read of what the previous launch wrote is gone).
+// EXPO_CHAIN_FUSE_STEPS=<k> forces the maximum (1: one kernel per step, the path before the fused kernel existed);
+// the default per regime is measured.  The reversed walk alternates the direction launch by launch and
+// the backward starts where the last forward launch ended: that plan keeps one launch per step.
+static int chain_fuse_steps(const ChainPlan& plan) {
+  static const int forced = env_int("EXPO_CHAIN_FUSE_STEPS", 0);
+  if (plan.snake) return 1;
+  const int k = forced > 0 ? forced : kChainFuseMax;
+  return k < kChainFuseMax ? k : kChainFuseMax;
+}
+
 extern "C" {
 
 int expo_version(void) { return EXPO_ABI_VERSION; }
@@ -2350,18 +2362,27 @@ int expo_chain_fwd(const int* filter_ids, int steps, void* const* acts, const fl
     if (int rc = chain_fork(fj, s)) return rc;
   }
   int rc = EXPO_OK;
+  // runs of up to `fuse` steps go into one launch each (chain_steps.hip); a shape off the vector path keeps one
+  // kernel per step, decided here once for the whole call
+  const int fuse = chain_steps_vec_path(acts, steps, h, w, dtype) ? chain_fuse_steps(plan) : 1;
   // chunk-major: every chunk (a tile, or half a tile per stream) goes through all the steps before the next one starts
   for (size_t c = 0; c < plan.chunks.size() && !rc; ++c) {
     const ChainChunk& ck = plan.chunks[c];
     hipStream_t sp = ck.lane ? fj->helper : s;
     const size_t ioff = size_t(ck.nb) * h * w * 3 * esz;
-    for (int i = 0; i < steps && !rc; ++i) {
-      const int rev = plan.snake ? (i & 1) : 0;
-      const void* xin = static_cast<const char*>(acts[i]) + ioff;
-      void* yout = static_cast<char*>(acts[i + 1]) + ioff;
-      const float* prm = params[i] + size_t(ck.nb) * kNumParams[filter_ids[i]];
-      rc = dtype == EXPO_F16 ? fwd_by_id<half_t>(filter_ids[i], xin, yout, prm, ck.np, h, w, sp, rev, n)
-                             : fwd_by_id<float>(filter_ids[i], xin, yout, prm, ck.np, h, w, sp, rev, n);
+    int cnt = 1;
+    for (int i = 0; i < steps && !rc; i += cnt) {
+      cnt = steps - i < fuse ? steps - i : fuse;
+      if (cnt > 1) {
+        rc = chain_steps_fwd(filter_ids + i, cnt, acts + i, params + i, ck.nb, ck.np, h, w, dtype, n, sp);
+      } else {
+        const int rev = plan.snake ? (i & 1) : 0;
+        const void* xin = static_cast<const char*>(acts[i]) + ioff;
+        void* yout = static_cast<char*>(acts[i + 1]) + ioff;
+        const float* prm = params[i] + size_t(ck.nb) * kNumParams[filter_ids[i]];
+        rc = dtype == EXPO_F16 ? fwd_by_id<half_t>(filter_ids[i], xin, yout, prm, ck.np, h, w, sp, rev, n)
+                               : fwd_by_id<float>(filter_ids[i], xin, yout, prm, ck.np, h, w, sp, rev, n);
+      }
     }
   }
   if (fj) {  // always joined, also on an error path: a forked helper must not stay outside the caller's stream order

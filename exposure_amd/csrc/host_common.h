@@ -111,6 +111,14 @@ int chain_records(void* workspace, size_t workspace_bytes, int n, int h, int w, 
 int finish_chain_fused(const int32_t* ids, const float* params, float* dparams, const float* records,
                        size_t step_floats, int steps, int n, int blocks_x, hipStream_t s);
 
+// defined in chain_steps.hip, used by expo_chain_fwd.  chain_steps_vec_path: do these activations run on the dwordx3
+// vector path (in every chunk of the plan)?  If so chain_steps_fwd enqueues steps [0, cnt) of ids / acts / params
+// (cnt <= kChainFuseMax) on images [nb, nb + np) as ONE launch with the geometry of a batch of n_geom images.
+constexpr int kChainFuseMax = 8;
+bool chain_steps_vec_path(void* const* acts, int steps, int h, int w, int dtype);
+int chain_steps_fwd(const int* ids, int cnt, void* const* acts, const float* const* params, int nb, int np, int h,
+                    int w, int dtype, int n_geom, hipStream_t s);
+
 inline int check_common(int n, int h, int w, int dtype) {
   if (n < 0 || h < 1 || w < 1) return fail(EXPO_E_BADARG, "n >= 0, h >= 1, w >= 1 required");
   if (n > 65535) return fail(EXPO_E_BADARG, "n > 65535 not supported (grid.y)");

@@ -226,7 +226,13 @@ int expo_finish_bwd(const int* filter_ids, int steps, const float* const* params
 
 /*
  * The benchmark construct of SURVEY.md section 8(d): `steps` filters applied
- * sequentially, one kernel per step, enqueued by a single call.
+ * sequentially, enqueued by a single call.  The forward runs up to 8 consecutive steps of a
+ * chunk of the plan in ONE launch (csrc/chain_steps.hip): a pixel group is loaded once, and after
+ * every step it is rounded to the storage type, stored to acts[k+1] and carried on in registers,
+ * so every acts[k+1] holds the very bits a per-step expo_filter_fwd would have written.
+ * EXPO_CHAIN_FUSE_STEPS=<k> in the environment (read once per process) caps the steps per launch;
+ * 1 is one kernel per step.  Shapes off the 12-byte vector path (odd fp16 pixel counts, unaligned
+ * bases) and the reversed walk (below) keep one kernel per step.  The backward is one kernel per step.
  *   filter_ids  host int [steps]
  *   acts        host array of steps+1 device image pointers: acts[0] = input,
  *               acts[i+1] = output of step i (kept: the backward reads them)
