@@ -94,6 +94,8 @@ SIGNATURES = {
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
+    'expo_bilinear_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
+                                         ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_chain_fused_bwd': (_i, [_vp, _fp, _i, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_critic_stats': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_overexposure_penalty': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -711,6 +713,34 @@ def area_resize_ragged(xs, windows, S, out):
                                        _dtype_code(xs[0]) if n else EXPO_F32,
                                        rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), q, int(S), _ptr(out),
                                        _dtype_code(out), _stream()), 'expo_area_resize_ragged')
+  return out
+
+
+def bilinear_resize_ragged(xs, windows, S, out):
+  """``expo_bilinear_resize_ragged``: plain bilinear resampling (half-pixel centres, no antialiasing: ``make_low_res``)
+  of square windows of linear images, in one ragged call.  Arguments as ``area_resize_ragged``; a window may be smaller
+  than S."""
+  import numpy as np
+  lib = load()
+  rec = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 4))
+  q, n = rec.shape[0], len(xs)
+  _img(out, 'out')
+  if tuple(out.shape) != (q, S, S, 3):
+    raise ExposureHipError('exposure_amd: out must be (%d, %d, %d, 3), got %s' % (q, S, S, tuple(out.shape)))
+  if q == 0:
+    return out
+  hs, ws = [0] * n, [0] * n
+  for i, x in enumerate(xs):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != out.device or not x.is_contiguous() or \
+        x.shape[-1] != 3 or not (x.dim() == 3 or (x.dim() == 4 and x.shape[0] == 1)) or x.dtype != xs[0].dtype:
+      raise ExposureHipError('exposure_amd: xs[%d] must be a contiguous (H, W, 3) or (1, H, W, 3) tensor of one dtype on '
+                             'the device of out (HIP path only, no CPU fallback)' % i)
+    hs[i], ws[i] = x.shape[-3], x.shape[-2]
+  with torch.cuda.device(out.device):
+    _check(lib.expo_bilinear_resize_ragged(_ptr_array(xs) if n else None, (ctypes.c_int * n)(*hs),
+                                           (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]) if n else EXPO_F32,
+                                           rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), q, int(S), _ptr(out),
+                                           _dtype_code(out), _stream()), 'expo_bilinear_resize_ragged')
   return out
 
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Ten translation units; extra arguments go to every compile step.
+# Eleven translation units; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
@@ -14,6 +14,8 @@
 #   decode.hip           the integer codes of an input image to the linear storage tensor (default flags: its
 #                        normalising division must stay IEEE)
 #   datasets.hip         the training sets' INTER_AREA master pack and its per-epoch re-cut (default flags)
+#   proxy.hip            the agent's bilinear 64x64 proxies of a ragged batch (-ffp-contract=off: every operation of
+#                        its definition is rounded on its own, so the host restatement matches bit for bit)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -43,6 +45,8 @@ p8=$!
 p9=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps.hip" -o "$TMP/chain_steps.o" &
 p10=$!
+"$HIPCC" "${FLAGS[@]}" -ffp-contract=off "$@" -c "$HERE/proxy.hip" -o "$TMP/proxy.o" &
+p11=$!
 # (a bare `wait` returns 0 whatever the jobs did: wait for each PID so a failed compile stops the script here)
 wait $p1
 wait $p2
@@ -54,5 +58,6 @@ wait $p7
 wait $p8
 wait $p9
 wait $p10
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" -o "$OUT"
+wait $p11
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

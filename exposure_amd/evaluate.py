@@ -43,6 +43,33 @@ def make_low_res(high_res, size):
   return low.permute(0, 2, 3, 1).contiguous().to(high_res.dtype)
 
 
+def center_windows(shapes):
+  """``get_image_center``'s slices as window rows: for every (H, W) of ``shapes`` the row (i, y0, x0, side) of the
+  largest centred square of image i (what ``_cabi.bilinear_resize_ragged`` / ``area_resize_ragged`` take)."""
+  rows = []
+  for i, (h, w) in enumerate(shapes):
+    h, w = int(h), int(w)
+    rows.append((i, (h - w) // 2, 0, w) if h > w else (i, 0, (w - h) // 2, h))
+  return rows
+
+
+def make_low_res_batch(images, size):
+  """``make_low_res`` of N images of ANY sizes in ONE call (``expo_bilinear_resize_ragged``): images are device tensors
+  (H_i, W_i, 3) or (1, H_i, W_i, 3) of one dtype; returns the stacked (N, size, size, 3) proxies in that dtype.  The
+  kernel reads the 4 size^2 taps of each image where they are: no fp32 copy of the centre square, no per-image launch.
+  Its float32 operations are rounded one by one; torch's may be contracted, so a value can differ from
+  ``make_low_res``'s in the last place."""
+  from . import _cabi
+  xs = [im.contiguous() for im in images]
+  if not xs:
+    raise ValueError('make_low_res_batch: no images')
+  out = torch.empty((len(xs), size, size, 3), dtype=xs[0].dtype, device=xs[0].device)
+  return _cabi.bilinear_resize_ragged(xs, center_windows([x.shape[-3:-1] for x in xs]), size, out)
+
+
+PROXIES = ('torch', 'device')
+
+
 def fused_chain(high_res, filter_ids, params24):
   """Apply a per-image sequence of filters to the full-resolution image in ONE pass
   (``expo_chain_fused_fwd``).  filter_ids: (N, steps) int32 C-ABI ids; params24: (N, steps, 24)."""
@@ -146,7 +173,7 @@ def _trace_result(out, low, states, trace, abi_ids, params, return_trace):
 
 @torch.no_grad()
 def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trace=False, fused=True,
-            intermediates=None):
+            intermediates=None, proxy='torch', picture=False):
   """Run the 5-step retouching loop.  ``high_res``: NHWC device tensor (fp16/fp32), linear RGB.
   Returns (retouched_high_res, retouched_low_res, states[, trace of selected filter ids][, intermediates]).
 
@@ -159,10 +186,17 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   (filter id, parameters); the full-resolution image is then read once, pushed through all steps
   in registers and written once.  ``fused=False`` is the reference's schedule (``net.py:796-821``):
   every step also filters the full-resolution tensor and feeds it back -- identical maths, one
-  fp16 rounding per step, ``steps`` times the HBM traffic."""
+  fp16 rounding per step, ``steps`` times the HBM traffic.
+
+  ``proxy='device'`` makes the 64x64 proxies with ``make_low_res_batch`` (one HIP launch) instead of torch's
+  interpolate; ``'torch'`` (default) is ``make_low_res``.  ``picture=True`` appends the (N, H, W, 3) uint8 picture of
+  the result (``save_png``'s encoding) as the last entry: on the fused path an EXPO_TAP_U8 tap of the last executed
+  step, written by the pass that writes the output; otherwise ``encode_u8`` of it."""
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
+  if proxy not in PROXIES:
+    raise ValueError('proxy must be one of %s' % (PROXIES,))
   if cfg.masking:
     fused = False  # the spatial mask depends on the running image: no parameters-only replay
   generic = any(f.uses_generic_kernels() for f in agent.filters)
@@ -171,7 +205,10 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   steps = steps or cfg.test_steps
   n = high_res.shape[0]
   dev = high_res.device
-  low = make_low_res(high_res, cfg.source_img_size)
+  if proxy == 'device':
+    low = make_low_res_batch(list(high_res.unbind(0)), cfg.source_img_size)
+  else:
+    low = make_low_res(high_res, cfg.source_img_size)
   if z is None:
     z = torch.rand((n, cfg.z_dim), device=dev)
   hi = high_res.contiguous()
@@ -179,8 +216,16 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
       agent, low, z, steps, dropout_masks, hi=None if fused else hi, generic=generic,
       keep_hi=bool(intermediates) and not fused)
   mask = _intermediate_mask(stops)
-  inter = None
-  if fused and intermediates:
+  inter = pic = None
+  last = 1 << (len(stops) - 1)  # the last executed step: its u8 tap is the picture of the output
+  if fused and picture and intermediates != 'storage':
+    # one pass: the output, the picture and (u8) the intermediates, which are the taps before the last
+    hi, taps = fused_chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1),
+                                (mask if intermediates else 0) | last, torch.uint8)
+    pic = taps[-1]
+    if intermediates:
+      inter = taps if mask & last else taps[:-1]
+  elif fused and intermediates:
     hi, inter = fused_chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), mask,
                                  torch.uint8 if intermediates == 'u8' else hi.dtype)
   elif fused:
@@ -192,12 +237,15 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
       inter = torch.stack(kept) if kept else torch.empty((0,) + tuple(hi.shape), dtype=hi.dtype, device=hi.device)
       if intermediates == 'u8':
         inter = encode_u8(inter)
+  if picture and pic is None:
+    pic = encode_u8(hi)
   res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace)
-  return res + (inter,) if intermediates else res
+  return res + ((inter,) if intermediates else ()) + ((pic,) if picture else ())
 
 
 @torch.no_grad()
-def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False, intermediates=None):
+def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False, intermediates=None,
+                  proxy='torch', picture=False):
   """``retouch`` over a list of images of ANY sizes at once (the batching ``evaluate.py:18`` asks for, without its
   same-resolution restriction).  ``images``: N device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype and device.
   One 64x64 proxy per image (``make_low_res``) is stacked, the agent runs once on the (N, 64, 64, 3) stack, and the
@@ -211,10 +259,14 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
   still drawn once for the batch when not given), and the per-image results are concatenated.
 
   ``intermediates`` as in ``retouch`` appends a list of N (S-1, H_i, W_i, 3) tensors; on the fused path they come from
-  the ragged launch itself (``fused_chain_ragged_taps``)."""
+  the ragged launch itself (``fused_chain_ragged_taps``).  ``proxy`` and ``picture`` as in ``retouch``: ``'device'``
+  builds all N proxies in one launch (``make_low_res_batch``) instead of ``make_low_res`` per image, and
+  ``picture=True`` appends a list of N (H_i, W_i, 3) uint8 pictures, from the ragged launch that writes the outputs."""
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
+  if proxy not in PROXIES:
+    raise ValueError('proxy must be one of %s' % (PROXIES,))
   images = list(images)
   n = len(images)
   if n == 0:
@@ -234,18 +286,35 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     for i, im in enumerate(hi4):
       masks = None if dropout_masks is None else [tuple(m[i:i + 1] for m in step) for step in dropout_masks]
       rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=masks, return_trace=return_trace or True,
-                          intermediates=intermediates))
+                          intermediates=intermediates, proxy=proxy, picture=picture))
     outs = [r[0].reshape(im.shape) for r, im in zip(rows, images)]
     low, states = torch.cat([r[1] for r in rows]), torch.cat([r[2] for r in rows])
     extra = ([r[4][:, 0] for r in rows],) if intermediates else ()
+    if picture:
+      extra += ([r[-1][0] for r in rows],)
     if return_trace == 'full':
       return (outs, low, states, {k: torch.cat([r[3][k] for r in rows]) for k in rows[0][3]}) + extra
     if return_trace:
       return (outs, low, states, torch.cat([r[3] for r in rows])) + extra
     return (outs, low, states) + extra
-  low = torch.cat([make_low_res(im, cfg.source_img_size) for im in hi4])
+  if proxy == 'device':
+    low = make_low_res_batch(images, cfg.source_img_size)
+  else:
+    low = torch.cat([make_low_res(im, cfg.source_img_size) for im in hi4])
   low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks)
   ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
+  if picture and intermediates != 'storage':
+    # one ragged launch: the outputs, the pictures and (u8) the intermediates, which are the taps before the last
+    mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
+    outs, taps = fused_chain_ragged_taps(images, ids, prm, (mask if intermediates else 0) | last, torch.uint8)
+    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+    if intermediates:
+      res += ([t if mask & last else t[:-1] for t in taps],)
+    return res + ([t[-1] for t in taps],)
+  if picture:  # storage intermediates: the taps of a launch have one format, so the pictures are encoded from the outputs
+    outs, inter = fused_chain_ragged_taps(images, ids, prm, _intermediate_mask(stops), images[0].dtype)
+    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+    return res + (inter, [encode_u8(o.reshape(o.shape[-3:])) for o in outs])
   if not intermediates:
     outs = fused_chain_ragged(images, ids, prm)
     return _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
@@ -368,7 +437,8 @@ def save_png_u8(path, img_u8):
 
 
 def tone_mapped_input(linear):
-  """``net.py:822-823``: max to white, then gamma 1/2.4 -- the ``input_tone_mapped`` picture of ``GAN.eval``."""
+  """``net.py:822-823``: max to white, then gamma 1/2.4 -- the ``input_tone_mapped`` picture of ``GAN.eval``.  Host
+  maths also with ``--device-png``: a device ``pow`` cannot be made bit-identical to numpy's."""
   a = np.asarray(linear, dtype=np.float32)
   return (a / a.max())**(1 / 2.4)
 
@@ -438,6 +508,15 @@ def main(argv=None):
   ap.add_argument('--device-decode', action='store_true',
                   help='read the images as integer codes (load_raw) and linearise them on the GPU, one ragged call per '
                   'group of --batch images (decode_images): the same tensors as the default host decode')
+  ap.add_argument('--device-proxy', action='store_true',
+                  help="make the agent's 64x64 proxies with one HIP launch per group of --batch images "
+                  '(make_low_res_batch) instead of torch\'s interpolate per image.  Same definition, every float32 '
+                  'operation rounded on its own: a proxy value can differ from the default path\'s in the last place, '
+                  'which in rare cases changes an argmax and with it the chosen filters')
+  ap.add_argument('--device-png', action='store_true',
+                  help='write <output>.png from 8-bit values made on the GPU: on the fused paths a tap of the last step '
+                  'from the pass that writes the output, with --stepwise an encode of the result.  The same pixels as '
+                  '--png, which it implies; --show-input\'s picture keeps its host maths')
   args = ap.parse_args(argv)
   dev = torch.device(CLI_DEVICE)
   if args.seed is not None:
@@ -457,14 +536,15 @@ def main(argv=None):
   dt = torch.float16 if args.dtype == 'f16' else torch.float32
   if args.batch < 1:
     ap.error('--batch must be >= 1')
-  if args.step_by_step:
+  if args.step_by_step or args.device_png:
     args.png = True
+  proxy = 'device' if args.device_proxy else 'torch'
   inter_kind = 'u8' if args.step_by_step else None
   records = []
 
-  def emit(path, hi, out, states, ops, inter=None):
+  def emit(path, hi, out, states, ops, inter=None, pic=None):
     """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows; inter: its
-    (S-1, H, W, 3) uint8 intermediates with --step-by-step)"""
+    (S-1, H, W, 3) uint8 intermediates with --step-by-step; pic: its (H, W, 3) uint8 picture with --device-png)"""
     trace = ops['selected']
     names = [agent.filters[int(j)].get_short_name() for j in trace[0]]
     print('%s: %dx%d  filters: %s' % (path, hi.shape[2], hi.shape[1], ' '.join(names)))
@@ -474,7 +554,10 @@ def main(argv=None):
     pngs = {}
     if args.png:
       stem = dst[:-4] if dst.endswith('.npy') else dst
-      pngs['retouched'] = save_png(stem + '.png', result)
+      if pic is not None:
+        pngs['retouched'] = save_png_u8(stem + '.png', pic.cpu().numpy())
+      else:
+        pngs['retouched'] = save_png(stem + '.png', result)
       if args.show_input:
         pngs['input_tone_mapped'] = save_png(stem + '.input_tone_mapped.png', tone_mapped_input(hi[0].float().cpu().numpy()))
       if inter is not None:
@@ -495,16 +578,20 @@ def main(argv=None):
   if args.batch == 1 or args.stepwise:
     for path in args.images:
       hi, = load_group([path])
-      res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind)
-      emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None)
+      res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
+                    picture=args.device_png)
+      emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None,
+           res[-1][0] if args.device_png else None)
     return records
   for b in range(0, len(args.images), args.batch):
     paths = args.images[b:b + args.batch]
     his = load_group(paths)
-    res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind)
+    res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
+                        picture=args.device_png)
     outs, states, ops = res[0], res[2], res[3]
     for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
-      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None)
+      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
+           res[-1][i] if args.device_png else None)
   return records
 
 

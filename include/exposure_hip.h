@@ -55,7 +55,7 @@ extern "C" {
                               kernels, expo_build_info; 7: expo_net_inputs, the first FC layer with its K dimension split
                               (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
                               9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged,
-                              expo_area_resize_ragged, expo_pack_recut */
+                              expo_area_resize_ragged, expo_pack_recut, expo_bilinear_resize_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -401,6 +401,31 @@ int expo_area_resize_ragged(const void* const* xs, const int* hs, const int* ws,
                             const int32_t* windows, int q, int S, void* out, int out_dtype, void* stream);
 int expo_pack_recut(const void* master, int m, int S, const int32_t* records, int count, int C, void* out, int dtype,
                     void* stream);
+
+/*
+ * Proxies (proxy.hip): the agent's low-resolution view of a ragged batch.  An added export of ABI 9 (the version is
+ * unchanged).
+ *
+ * expo_bilinear_resize_ragged: q square windows of n linear NHWC images, each resampled to S x S x 3 with plain
+ * bilinear interpolation at half-pixel centres, no antialiasing -- net.py:779 (cv2.resize(get_image_center(hi),
+ * (64, 64)), the proxy the agent decides on) and data_provider.py:97, 137 (cv2.resize(img, output_size) without
+ * augmentation); the arithmetic is torch's upsample_bilinear2d(align_corners=False, antialias=False), every operation
+ * an individually rounded float32 operation, nothing contracted:
+ *     scale  = (float)side / (float)S
+ *     src(d) = max(scale * ((float)d + 0.5f) - 0.5f, 0.0f)
+ *     i0 = (int)src;  i1 = i0 + (i0 < side - 1);  l1 = src - (float)i0;  l0 = 1.0f - l1
+ *     v = hl0 * (wl0 * a + wl1 * b) + hl1 * (wl0 * c + wl1 * d)     a, b = row i0 at columns j0, j1; c, d = row i1
+ *     out = cast(v), round to nearest even; the taps are widened to float32 first.
+ *   xs, hs, ws, windows as for expo_area_resize_ragged (HOST arrays; windows [q][4] = (image, y0, x0, side)).
+ *   out        device [q][S][S][3] in out_dtype, window k at out[k].
+ * side < S (upscaling) is allowed and side == S is the identity up to the cast.  The call reads 4 S^2 pixels of a
+ * window whatever its side.  No atomics, no workspace: a window's result is bit-identical run to run and whatever
+ * else the call holds.  64 windows per launch, more as further launches on `stream`.  Validated before anything is
+ * enqueued (EXPO_E_BADARG / EXPO_E_BADDTYPE): n, q >= 0, dtypes, no null pointer, h, w >= 1 and one image < 2 GiB,
+ * every window inside its image with side >= 1, 1 <= S <= 4096; q == 0 is a no-op.
+ */
+int expo_bilinear_resize_ragged(const void* const* xs, const int* hs, const int* ws, int n, int in_dtype,
+                                const int32_t* windows, int q, int S, void* out, int out_dtype, void* stream);
 
 /*
  * One-pass backward of the same fixed per-image sequence: dx = d(loss)/dx and every step's parameter
