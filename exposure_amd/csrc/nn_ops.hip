@@ -370,6 +370,7 @@ __global__ __launch_bounds__(64) void agent_select_fwd_kernel(const SelectArgs a
     usage_pen += u * oh;
     ns[3 + i] = fmaxf(u, oh);
   }
+  for (int c = 3 + K; c < a.state_dim; ++c) ns[c] = st[c];  // whatever a caller keeps behind the usage flags: copied through
   surrogate[img] = (id >= 0 && id < K) ? logf(p[id] + 1e-10f) : 0.0f;
   const float ent_pen = (1.0f - progress[0]) * a.exploration_penalty * (-H + logf(float(K)));
   pen_base[img] = ent_pen + usage_pen * a.usage_penalty + (1.0f - submitted) * submitted * a.early_stop_penalty;

@@ -565,7 +565,8 @@ int expo_heads_regress_bwd(const float* const* raw, float* const* draw, const in
  *   submitted = |step + 1 - test_steps| < 1e-4;  penalty_base = (1 - progress) c_e (log K - entropy) + <usage, onehot> c_u
  *   + (1 - submitted) submitted c_s.
  * logits [n][k]; noise: element n * noise_stride (column 0 of z); states / new_states [n][state_dim] = [reward, stopped,
- * step, usage x k, ...]; progress: DEVICE float[1] (a graph input); consts: HOST float[5] = {cfg.exploration,
+ * step, usage x k, ...], state_dim >= 3 + k: columns c >= 3 + k are copied through, new_states[n][c] = states[n][c]
+ * (every element of new_states is written); progress: DEVICE float[1] (a graph input); consts: HOST float[5] = {cfg.exploration,
  * cfg.exploration_penalty, cfg.filter_usage_penalty, cfg.early_stop_penalty, cfg.test_steps}; outputs pdf / onehot
  * [n][k], entropy / surrogate / penalty_base [n], selected int32 [n].  expo_agent_select_bwd: d logits from the
  * gradients of surrogate and penalty_base (through the entropy); k <= 16.
