@@ -36,12 +36,45 @@ def area_matrix(side, S):
   return a
 
 
-def area_resize(img, S):
-  """(side, side, C) -> (S, S, C) float64."""
+def area_resize(img, S, cols=None):
+  """(side, side, C) -> (S, S, C) float64.  ``cols``: another (S, side) matrix for the column pass (the mutants of
+  tests/test_datasets_host.py)."""
   a = area_matrix(img.shape[0], S)
   img = np.asarray(img, dtype=np.float64)
   rows = np.tensordot(a, img, axes=(1, 0))                      # (S, side, C)
-  return np.tensordot(rows, a, axes=(1, 1)).transpose(0, 2, 1)  # (S, C, S) -> (S, S, C)
+  return np.tensordot(rows, a if cols is None else cols, axes=(1, 1)).transpose(0, 2, 1)  # (S, C, S) -> (S, S, C)
+
+
+BOUND = 4e-6  # |out - float64| of expo_area_resize_ragged's fp32 output on inputs in [0, 1]
+
+
+def max_err(got, want):
+  """The comparison of the device tests: the largest |got - want| and where it sits."""
+  err = np.abs(np.asarray(got, dtype=np.float64) - want)
+  return float(err.max()), tuple(int(i) for i in np.unravel_index(err.argmax(), err.shape))
+
+
+def tile_plan(side, S, tile_cols=4096):
+  """The column tiles of area_resize_kernel (csrc/datasets.hip: tile_out_cols and the loop over ox0) for one window:
+  [(ox0, ox1, c0, c1)], output columns [ox0, ox1) read from the source columns [c0, c1) held in one LDS tile."""
+  scale = side / S
+  per = int((tile_cols - 2) / scale)
+  assert per >= 1, 'side / S too large for one LDS tile: the entry point refuses the window'
+  plan = []
+  for ox0 in range(0, S, per):
+    ox1 = min(ox0 + per, S)
+    c0 = axis_weights(ox0, scale, side)[0][0]
+    c1 = axis_weights(ox1 - 1, scale, side)[-1][0] + 1
+    plan.append((ox0, ox1, c0, c1))
+  return plan
+
+
+# (S, side) -> output columns per tile: the windows of tests/test_hip_datasets.py::test_area_resize_across_tile_seams.
+# 4094 is the last single-tile side at S = 64, 4095 the first with a second tile (of one column), 5120 an integer scale
+# (every 1e-3 edge decision sits on an integer), 6000 a seam in the middle for both output sizes of the recipes, and
+# 8191 three tiles (8188 is the smallest side that gives three for any S).
+SEAM_PLANS = {(64, 4094): [64], (64, 4095): [63, 1], (64, 5120): [51, 13], (64, 6000): [43, 21], (80, 6000): [54, 26],
+              (64, 8191): [31, 31, 2]}
 
 
 # ---- stand-ins with the signatures of the _cabi calls (CPU tensors) --------------------------------------------------------

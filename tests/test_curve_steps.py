@@ -118,6 +118,26 @@ def run_curve(x, dy, p, curves, steps, dtype, dev, need_dx=True):
 @pytest.mark.parametrize('dtype', [torch.float16, torch.float32])
 @pytest.mark.parametrize('shape', [(3, 64, 64, 3), (2, 7, 5, 3), (1, 256, 192, 3)])
 def test_generic_curve_kernels_match_oracle(steps, curves, dtype, shape, gpu_device):
+  check_generic_curve(steps, curves, dtype, shape, gpu_device)
+
+
+# cg_blocks (csrc/curve_generic.hip) launches min(ceil(H W / 2048), 256) blocks of 256 threads per image; the largest shape
+# above, 256 x 192 = 49,152 pixels, gives 24 blocks.  768 x 704 = 540,672 pixels would give 264: the cap holds, the grid
+# stride is 256 x 256 = 65,536 pixels, the first 16,384 threads (64 blocks) accumulate 9 pixels in their private LDS columns
+# and the others 8, and the workspace holds 256 records per image where H W / 2048 says 264.  A non-power-of-two step count
+# (the on-knot exclusion) and the largest one, both curve counts, both dtypes; the full grid of step counts stays on the small
+# shapes (the float64 oracle over 1.6 M values is what these cases cost).
+@pytest.mark.gpu
+@pytest.mark.parametrize('steps', [5, 16])
+@pytest.mark.parametrize('curves', [1, 3])
+@pytest.mark.parametrize('dtype', [torch.float16, torch.float32])
+def test_generic_curve_kernels_match_oracle_past_the_block_cap(steps, curves, dtype, gpu_device):
+  shape = (1, 768, 704, 3)
+  assert shape[1] * shape[2] > 256 * 2048
+  check_generic_curve(steps, curves, dtype, shape, gpu_device)
+
+
+def check_generic_curve(steps, curves, dtype, shape, gpu_device):
   rng = np.random.default_rng(steps * 100 + curves * 10 + shape[1])
   fid = 4 if curves == 1 else 7
   x = (synthetic.make_images(rng, shape, NP_DT[dtype]).astype(np.float32) * 1.3 - 0.1).astype(NP_DT[dtype])

@@ -57,6 +57,57 @@ def test_the_thresholds():
     assert np.abs(ref.area_matrix(side, S).sum(axis=1) - 1).max() < 1e-3
 
 
+def sweep_sides(S):
+  """Sides around the first second tile of S = 64 / 80 (4095) and about 200 more up to 65535, odd strides."""
+  return sorted(set(range(4090, 4111)) | set(range(4111, 65536, 307)) | {S * 4094 // 64, 8188, 8191, 8192, 65535})
+
+
+def test_tile_plans_fit_the_lds_tile_and_the_seam_cases_are_multi_tile():
+  """area_resize_kernel trusts that a tile's source span fits its LDS buffer (``min(c1 - c0, kTileCols)`` must never
+  truncate) and the device tests of the seams trust the tile counts pinned here: a change of kTileCols or of
+  tile_out_cols shows up on the CPU, not as device cases that silently became single-tile."""
+  cases = [(S, side) for S in (64, 80) for side in sweep_sides(S)]
+  cases += [(1, 1), (1, 97), (1, 4094), (7, 7), (7, 4095), (7, 28657), (7, 28658), (256, 256), (256, 4095), (256, 4097),
+            (256, 20001), (256, 65535)]
+  for S, side in cases:
+    plan = ref.tile_plan(side, S)
+    assert plan[0][0] == 0 and plan[-1][1] == S and all(a[1] == b[0] for a, b in zip(plan, plan[1:])), (S, side)
+    for ox0, ox1, c0, c1 in plan:
+      assert ox1 > ox0 and 0 <= c0 < c1 <= side and c1 - c0 <= 4096, (S, side, ox0, ox1, c0, c1)
+    if side <= 4094:
+      assert len(plan) == 1, (S, side)
+  with pytest.raises(AssertionError):
+    ref.tile_plan(4095, 1)  # no output column fits a tile: expo_area_resize_ragged refuses such a window
+  for (S, side), widths in ref.SEAM_PLANS.items():
+    assert [ox1 - ox0 for ox0, ox1, _, _ in ref.tile_plan(side, S)] == widths, (S, side)
+  # the sides of tests/test_hip_datasets.py::sides() are all single-tile: the seams were untested before these cases
+  for S in (64, 80):
+    assert all(len(ref.tile_plan(side, S)) == 1 for side in (S, S + 1, 97, 2 * S, 239, 1000, 4001))
+
+
+def test_the_bound_rejects_a_shifted_and_a_dropped_second_tile():
+  """What a wrong seam would look like, through the comparison of the device tests (``ref.max_err`` against
+  ``ref.BOUND``), for side 6000 / S 64 (tiles of 43 and 21 output columns): the second tile read from source columns
+  one to the left (a ``c - c0`` off by one), and the second tile never written."""
+  side, S = 6000, 64
+  (_, split, _, _), (ox0, ox1, _, _) = ref.tile_plan(side, S)
+  assert (split, ox0, ox1) == (43, 43, 64)
+  img = np.random.default_rng(6000).random((side, side, 1), dtype=np.float32).astype(np.float64)
+  a = ref.area_matrix(side, S)
+  want = ref.area_resize(img, S)
+  assert ref.max_err(ref.area_resize(img, S, cols=a), want)[0] == 0.0
+  assert ref.max_err(want.astype(np.float32), want)[0] <= ref.BOUND  # the store's rounding alone is inside it
+  shifted = a.copy()
+  shifted[ox0:, :-1] = a[ox0:, 1:]  # output column ox reads source column c - 1 where it should read c
+  shifted[ox0:, -1] = 0.0
+  err, at = ref.max_err(ref.area_resize(img, S, cols=shifted), want)
+  assert err > 100 * ref.BOUND and at[1] >= ox0, (err, at)
+  dropped = want.copy()
+  dropped[:, ox0:] = 0.0
+  err, at = ref.max_err(dropped, want)
+  assert err > 100 * ref.BOUND and at[1] >= ox0, (err, at)
+
+
 # ---- files, folds, tables ----------------------------------------------------------------------------------------------------
 def test_files_are_sorted_and_folds_are_one_based(tmp_path):
   for name in ('c.png', 'a.png', 'b.png', 'd.png'):

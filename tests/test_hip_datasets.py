@@ -18,7 +18,7 @@ from tests import _area_ref as ref
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device('cuda:0')
-BOUND = 4e-6  # |out - float64| for fp32 output on inputs in [0, 1]
+BOUND = ref.BOUND  # 4e-6: |out - float64| for fp32 output on inputs in [0, 1]
 
 
 def sides(S):
@@ -80,6 +80,54 @@ def test_area_resize_is_deterministic_and_ragged_equals_single_windows():
   for k, win in enumerate(wins):
     one = resize([xs[win[0]]], [(0,) + tuple(win[1:])], 80, torch.float32)
     assert torch.equal(one[0], a[k]), k
+
+
+def seam_image(rng, side, in_dtype):
+  """One image a few pixels larger than the window, the window at an odd offset (as make_case places its windows).
+  -> (device image, window, the window's pixels in float64 on the host)"""
+  y0, x0 = 3, 1
+  img = torch.from_numpy(rng.random((side + 3, side + 2, 3), dtype=np.float32)).to(in_dtype)
+  return img.to(DEV), (0, y0, x0, side), img[y0:y0 + side, x0:x0 + side].double().numpy()
+
+
+@pytest.mark.parametrize('S,side', sorted(ref.SEAM_PLANS))
+def test_area_resize_across_tile_seams(S, side):
+  """Windows of more than kTileCols - 2 = 4094 source columns per S output columns: the kernel cuts the output columns
+  into several LDS tiles, each with its own first source column c0, re-using ``colsum`` behind a second barrier.  The
+  plans (tests/_area_ref.py::SEAM_PLANS, pinned against the restated tile arithmetic in tests/test_datasets_host.py):
+  64 | 63 + 1 | 51 + 13 (integer scale 80) | 43 + 21 | 54 + 26 (S = 80) | 31 + 31 + 2 output columns.  fp32 input up to
+  side 6000, fp16 input for 8191 (half the memory).  BOUND does not grow with the side: both passes accumulate in
+  double, and the only float32 roundings are ``colsum`` and the store."""
+  widths = [ox1 - ox0 for ox0, ox1, _, _ in ref.tile_plan(side, S)]
+  assert widths == ref.SEAM_PLANS[(S, side)] and (len(widths) > 1) == (side > 4094)
+  in_dtype = torch.float16 if side > 6000 else torch.float32
+  x, win, host = seam_image(np.random.default_rng(side + S), side, in_dtype)
+  want = ref.area_resize(host, S)
+  o32 = resize([x], [win], S, torch.float32)
+  err, at = ref.max_err(o32[0].cpu().numpy(), want)
+  print('area resize S = %d, side = %d, tiles %r: worst |err| %.3e = %.3f of BOUND at %r' % (S, side, widths, err, err / BOUND, at))
+  assert err <= BOUND, (err, at, widths)
+  o16 = resize([x], [win], S, torch.float16)
+  assert torch.equal(o16, o32.half())
+
+
+def test_a_multi_tile_window_does_not_depend_on_the_batch_or_the_launch():
+  """Side 5120 at S = 64 (tiles of 51 + 13 output columns) alone == the same window inside a ragged call between
+  single-tile windows (and once more at another offset of its image: other c0s against the same LDS), and == itself at a
+  second launch, bit for bit."""
+  rng = np.random.default_rng(11)
+  S, side = 64, 5120
+  assert len(ref.tile_plan(side, S)) == 2 and len(ref.tile_plan(239, S)) == 1
+  big, win, _ = seam_image(rng, side, torch.float32)
+  small = torch.from_numpy(rng.random((241, 243, 3), dtype=np.float32)).to(DEV)
+  wins = [(1, 0, 1, 97), (0,) + win[1:], (1, 2, 3, 239), (0, 0, 2, side), (1, 5, 0, 64)]
+  a = resize([big, small], wins, S, torch.float32)
+  b = resize([big, small], wins, S, torch.float32)
+  assert torch.equal(a, b)
+  for k, w in enumerate(wins):
+    one = resize([(big, small)[w[0]]], [(0,) + tuple(w[1:])], S, torch.float32)
+    assert torch.equal(one[0], a[k]), k
+  assert not torch.equal(a[1], a[3])  # (two different windows of the large image)
 
 
 @pytest.mark.parametrize('side', [239, 1000])

@@ -76,8 +76,63 @@ def test_bias_lrelu_autograd_wiring_cpu():
   np.testing.assert_allclose(gg_b.numpy(), np.broadcast_to(w.numpy(), y.shape) * lrelu_slope(pre), rtol=1e-6)
 
 
+# Shapes past the grid caps of csrc/nn_ops.hip (the largest shapes above them are exactly 2,097,152 elements: 2048 blocks
+# of lrelu_bwd_bias, one trip per thread).  A block is 256 threads, one float4 (or one float on the scalar path) per thread
+# and trip; lrelu_bwd_bias launches min(ceil(count / 1024), kBgMaxBlocks = 2048) blocks, bias_lrelu_fwd / lrelu_bwd
+# min(ceil(items / 256), 4096) (grid_for), items = count / 4 on the float4 path and count on the scalar one:
+#   (65, 32, 32, 32)    2,129,920 elements = 532,480 float4s: 2080 -> 2048 blocks of lrelu_bwd_bias, stride 524,288: the
+#                       first 8,192 threads (32 blocks) take a second trip, the others one; groups = 8
+#   (33, 16, 16, 256)   2,162,688 = 540,672 float4s: 2112 -> 2048 blocks, 16,384 threads (64 blocks) take a second trip;
+#                       groups = 64, the widest channel group (4 threads of a block share one)
+#   (129, 32, 32, 32)   4,227,072 = 1,056,768 float4s: 3 trips for the first 8,192 threads of lrelu_bwd_bias, 2 for the rest;
+#                       4128 -> 4096 blocks of bias_lrelu_fwd / lrelu_bwd (float4 path, stride 1,048,576: 8,192 threads
+#                       take a second trip)
+#   (1025, 1027)        1,052,675 elements (odd: the scalar paths): 4113 -> 4096 blocks, stride 1,048,576, 4,099 threads take
+#                       a second trip; 1,048,576 % 1027 = 9: the bias index moves between trips; 1027 channels: the bias
+#                       gradient is the separate column sum
+#   (193, 32, 32, 24)   4,743,168 = 1,185,792 float4s: 4632 -> 4096 blocks on the float4 path with a channel count that is
+#                       no power of two (4,194,304 % 24 = 16: the bias float4 of a thread changes between trips); nn_ops
+#                       routes the bias gradient to lrelu_bwd + the separate column sum (expo_lrelu_bwd_bias refuses 24
+#                       channels: test_lrelu_bwd_bias_refuses_channel_counts_that_are_no_power_of_two)
+# (the double backward of the largest shape takes well under a second: the second-order checks run for all of them)
+OVER_THE_GRID_CAPS = [(65, 32, 32, 32), (33, 16, 16, 256), (129, 32, 32, 32), (1025, 1027), (193, 32, 32, 24)]
+
+
+def test_a_bias_gradient_that_stops_after_one_trip_is_rejected():
+  """CPU: what lrelu_bwd_bias would return for (65, 32, 32, 32) if its threads left after one trip of 2048 x 256 float4s
+  (the first 65,536 of the 66,560 rows), and if the second trip landed one channel group further, through the assertion
+  the device test uses."""
+  shape = (65, 32, 32, 32)
+  rng = np.random.default_rng(1)
+  pre = rng.standard_normal(shape)
+  cols = (rng.standard_normal(shape) * lrelu_slope(pre)).reshape(-1, shape[-1])
+  ref, a = cols.sum(0), np.abs(cols).sum(0)
+  one_trip = 2048 * 256 * 4 // shape[-1]
+  assert 0 < one_trip < cols.shape[0] <= 2 * one_trip
+  assert_param_grad_close(cols.astype(np.float32).sum(0, dtype=np.float32), ref, a, 'an honest float32 sum')
+  for what, got in (('one trip', cols[:one_trip].sum(0)),
+                    ('the second trip in the next channel group', cols[:one_trip].sum(0) + np.roll(cols[one_trip:].sum(0), 4))):
+    with pytest.raises(AssertionError, match='out of tolerance'):
+      assert_param_grad_close(got, ref, a, what)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('shape', [(64, 32, 32, 32), (5, 128), (3, 7, 5, 6), (1, 3), (64, 4, 4, 256), (128, 16, 16, 64), (1, 4)])
+def test_lrelu_bwd_bias_refuses_channel_counts_that_are_no_power_of_two(gpu_device):
+  """24 channels: the float4 arithmetic of lrelu_bwd_bias_kernel (a thread keeps its channel group) needs 256 % (C / 4)
+  == 0.  The entry point refuses before it launches, and nn_ops asks lrelu_bwd_bias_supported first."""
+  from exposure_amd import _cabi
+  z = torch.randn((8, 24), device=gpu_device)
+  dy, db = torch.full_like(z, 7.0), torch.full((24,), 7.0, device=gpu_device)
+  assert not _cabi.lrelu_bwd_bias_supported(z, z)
+  with pytest.raises(_cabi.ExposureHipError, match='power of two'):
+    _cabi.lrelu_bwd_bias(z, z.clone(), dy, db)
+  torch.cuda.synchronize()
+  assert bool((dy == 7).all()) and bool((db == 7).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape', [(64, 32, 32, 32), (5, 128), (3, 7, 5, 6), (1, 3), (64, 4, 4, 256), (128, 16, 16, 64), (1, 4)] +
+                         OVER_THE_GRID_CAPS)
 def test_bias_lrelu_kernels_match_formula(shape, gpu_device):
   dev = gpu_device
   rng = np.random.default_rng(1)
