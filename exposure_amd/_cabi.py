@@ -96,6 +96,8 @@ SIGNATURES = {
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     'expo_bilinear_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                          ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
+    'expo_patch_stats': (_i, [_vp, _i, _i, _vp, _i, _i, _fp, _i, _vp]),
+    'expo_stat_hist': (_i, [_fp, _i, _i, _vp, _vp]),
     'expo_chain_fused_bwd': (_i, [_vp, _fp, _i, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_critic_stats': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
     'expo_overexposure_penalty': (_i, [_vp, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -763,6 +765,46 @@ def pack_recut(master, records, out):
     _check(lib.expo_pack_recut(_ptr(master), master.shape[0], master.shape[1], _ptr(records), count, c, _ptr(out),
                                _dtype_code(out), _stream()), 'expo_pack_recut')
   return out
+
+
+def patch_stats(master, records, C, stats):
+  """``expo_patch_stats``: stats[r] = [mean lum, 2 std lum, mean HLS saturation] of master[src_r][oy_r:oy_r + C,
+  ox_r:ox_r + C] (``metrics.get_statistics``, summed in double).  master (M, S, S, 3): contiguous device tensor, float16
+  or float32; records: contiguous device int32 tensor (count, 3) of (src, oy, ox); stats: contiguous device float32
+  tensor (count, 3)."""
+  lib = load()
+  _img(master, 'master')
+  if master.shape[1] != master.shape[2]:
+    raise ExposureHipError('exposure_amd: master must be (M, S, S, 3), got %s' % (tuple(master.shape),))
+  if not isinstance(records, torch.Tensor) or not records.is_cuda or records.device != master.device or \
+      records.dtype != torch.int32 or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 3:
+    raise ExposureHipError('exposure_amd: records must be a contiguous int32 device tensor of shape (count, 3) on the '
+                           'device of master (HIP path only, no CPU fallback)')
+  count = records.shape[0]
+  if not isinstance(stats, torch.Tensor) or stats.device != master.device:
+    raise ExposureHipError('exposure_amd: stats must be a tensor on the device of master')
+  _f32(stats, 'stats', (count, 3))
+  with torch.cuda.device(master.device):
+    _check(lib.expo_patch_stats(_ptr(master), master.shape[0], master.shape[1], _ptr(records), count, int(C),
+                                _ptr(stats), _dtype_code(master), _stream()), 'expo_patch_stats')
+  return stats
+
+
+def stat_hist(stats, bins, counts):
+  """``expo_stat_hist``: counts[k][b] = how many stats[:, k] fall in bin b of ``bins`` equal bins over [0, 1]
+  (``np.histogram(range=(0, 1))``; values outside and NaN are dropped).  stats: contiguous device float32 tensor
+  (q, 3); counts: contiguous device int32 tensor (3, bins), fully overwritten."""
+  lib = load()
+  if not isinstance(stats, torch.Tensor) or stats.dim() != 2:
+    raise ExposureHipError('exposure_amd: stats must be a (q, 3) tensor')
+  _f32(stats, 'stats', (stats.shape[0], 3))
+  if not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.device != stats.device or \
+      counts.dtype != torch.int32 or not counts.is_contiguous() or tuple(counts.shape) != (3, int(bins)):
+    raise ExposureHipError('exposure_amd: counts must be a contiguous int32 device tensor of shape (3, %d) on the '
+                           'device of stats' % int(bins))
+  with torch.cuda.device(stats.device):
+    _check(lib.expo_stat_hist(_ptr(stats), stats.shape[0], int(bins), _ptr(counts), _stream()), 'expo_stat_hist')
+  return counts
 
 
 FUSED_BWD_MAX_STEPS = 8  # EXPO_FUSED_BWD_MAX_STEPS

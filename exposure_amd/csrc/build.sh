@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Eleven translation units; extra arguments go to every compile step.
+# Twelve translation units; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
@@ -16,6 +16,7 @@
 #   datasets.hip         the training sets' INTER_AREA master pack and its per-epoch re-cut (default flags)
 #   proxy.hip            the agent's bilinear 64x64 proxies of a ragged batch (-ffp-contract=off: every operation of
 #                        its definition is rounded on its own, so the host restatement matches bit for bit)
+#   metric.hip           the evaluation metric's patch statistics and their histograms (default flags)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -47,6 +48,8 @@ p9=$!
 p10=$!
 "$HIPCC" "${FLAGS[@]}" -ffp-contract=off "$@" -c "$HERE/proxy.hip" -o "$TMP/proxy.o" &
 p11=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/metric.hip" -o "$TMP/metric.o" &
+p12=$!
 # (a bare `wait` returns 0 whatever the jobs did: wait for each PID so a failed compile stops the script here)
 wait $p1
 wait $p2
@@ -59,5 +62,6 @@ wait $p8
 wait $p9
 wait $p10
 wait $p11
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" -o "$OUT"
+wait $p12
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -517,6 +517,14 @@ def main(argv=None):
                   help='write <output>.png from 8-bit values made on the GPU: on the fused paths a tap of the last step '
                   'from the pass that writes the output, with --stepwise an encode of the result.  The same pixels as '
                   '--png, which it implies; --show-input\'s picture keeps its host maths')
+  ap.add_argument('--score', default=None, metavar='TARGET_DIR',
+                  help="after the run, score the retouched pictures against the 8-bit pictures of TARGET_DIR with the "
+                  "paper's metric (histogram intersection of luminance, contrast and saturation, exposure_amd.metrics) "
+                  'on the GPU: the pictures of --device-png, which it implies, stay on the device and no PNG is read '
+                  'back.  Prints the two lines of histogram_intersection.py and appends dict(score, average) to the '
+                  'returned records')
+  ap.add_argument('--score-seed', type=int, default=None, metavar='N',
+                  help="seeds the metric's random crops (default: a different sample every run, as the script)")
   args = ap.parse_args(argv)
   dev = torch.device(CLI_DEVICE)
   if args.seed is not None:
@@ -536,11 +544,14 @@ def main(argv=None):
   dt = torch.float16 if args.dtype == 'f16' else torch.float32
   if args.batch < 1:
     ap.error('--batch must be >= 1')
+  if args.score:
+    args.device_png = True
   if args.step_by_step or args.device_png:
     args.png = True
   proxy = 'device' if args.device_proxy else 'torch'
   inter_kind = 'u8' if args.step_by_step else None
   records = []
+  pictures = []  # --score: every emitted image's uint8 picture, kept on the device (not the float outputs)
 
   def emit(path, hi, out, states, ops, inter=None, pic=None):
     """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows; inter: its
@@ -551,6 +562,8 @@ def main(argv=None):
     dst = output_path(args.out, path, len(args.images) > 1)
     result = out[0].float().cpu().numpy()
     np.save(dst, result)
+    if args.score:
+      pictures.append(pic.contiguous())
     pngs = {}
     if args.png:
       stem = dst[:-4] if dst.endswith('.npy') else dst
@@ -582,16 +595,25 @@ def main(argv=None):
                     picture=args.device_png)
       emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None,
            res[-1][0] if args.device_png else None)
-    return records
-  for b in range(0, len(args.images), args.batch):
-    paths = args.images[b:b + args.batch]
-    his = load_group(paths)
-    res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
-                        picture=args.device_png)
-    outs, states, ops = res[0], res[2], res[3]
-    for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
-      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
-           res[-1][i] if args.device_png else None)
+  else:
+    for b in range(0, len(args.images), args.batch):
+      paths = args.images[b:b + args.batch]
+      his = load_group(paths)
+      res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
+                          picture=args.device_png)
+      outs, states, ops = res[0], res[2], res[3]
+      for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
+        emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
+             res[-1][i] if args.device_png else None)
+  if args.score:
+    import random
+    from . import metrics
+    rng = random.Random(args.score_seed) if args.score_seed is not None else None
+    ints, avg = metrics.score(metrics.set_statistics(pictures, rng, names=args.images),
+                              metrics.read_statistics(args.score, rng=rng, device=dev))
+    for line in metrics.format_score(ints, avg):
+      print(line)
+    records.append(dict(score=ints, average=avg))
   return records
 
 

@@ -55,7 +55,8 @@ extern "C" {
                               kernels, expo_build_info; 7: expo_net_inputs, the first FC layer with its K dimension split
                               (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
                               9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged,
-                              expo_area_resize_ragged, expo_pack_recut, expo_bilinear_resize_ragged */
+                              expo_area_resize_ragged, expo_pack_recut, expo_bilinear_resize_ragged,
+                              expo_patch_stats, expo_stat_hist */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -426,6 +427,38 @@ int expo_pack_recut(const void* master, int m, int S, const int32_t* records, in
  */
 int expo_bilinear_resize_ragged(const void* const* xs, const int* hs, const int* ws, int n, int in_dtype,
                                 const int32_t* windows, int q, int S, void* out, int out_dtype, void* stream);
+
+/*
+ * The evaluation metric (metric.hip): histogram_intersection.py's statistics of patches and their histograms.  Added
+ * exports of ABI 9 (the version is unchanged).
+ *
+ * expo_patch_stats: stats[r] = the three statistics of the crop master[src_r][oy_r : oy_r + C, ox_r : ox_r + C].
+ *   master     device [m][S][S][3] in dtype (EXPO_F16 / EXPO_F32).
+ *   records    DEVICE int32 [count][3] = (src, oy, ox); out of range is the caller's contract (clamped on the device,
+ *              so no read leaves the master).
+ *   stats      device float32 [count][3], fully overwritten.  Every value is widened to double and clipped to [0, 1];
+ *              with l = .27 R + .67 G + .06 B in double:
+ *                stats[r][0] = mean(l)
+ *                stats[r][1] = 2 sqrt(max(mean(l^2) - mean(l)^2, 0))        (the population std)
+ *                stats[r][2] = mean(s),  s = 0 where max == min, else (max - min) / max(den, 1e-12) with
+ *                              den = (max + min) / 2 < 0.5 ? max + min : 2 - max - min      (HLS saturation)
+ *              each rounded once to float32.  The two luminance sums are taken of l - l0, l0 the crop's first pixel
+ *              (the same mean and variance): a constant crop has std exactly 0.
+ * One block per record; every sum runs in a fixed order in double (per-thread partials over a fixed pixel assignment,
+ * then a fixed LDS tree), no atomics: a row is bit-identical run to run and whatever else the call holds.
+ *
+ * expo_stat_hist: counts[k][b] = the number of stats[.][k] in bin b of `bins` equal bins over [0, 1], as
+ * np.histogram(range=(0, 1)): a float32 v with 0 <= v <= 1 goes to bin min((int)(v * bins), bins - 1) (the product in
+ * float32: exact for bins a power of two), anything else (v < 0, v > 1, NaN) is dropped.
+ *   stats      device float32 [q][3];  counts  device int32 [3][bins], fully overwritten (q == 0 writes zeros).
+ * One block, integer LDS atomics (the counts do not depend on the order).
+ *
+ * Both validate before anything is enqueued (EXPO_E_BADARG / EXPO_E_BADDTYPE): count, q >= 0, the dtype, 1 <= C <= S,
+ * m >= 1, 1 <= bins <= 1024, no null pointer; expo_patch_stats with count == 0 is a no-op.
+ */
+int expo_patch_stats(const void* master, int m, int S, const int32_t* records, int count, int C, float* stats,
+                     int dtype, void* stream);
+int expo_stat_hist(const float* stats, int q, int bins, int32_t* counts, void* stream);
 
 /*
  * One-pass backward of the same fixed per-image sequence: dx = d(loss)/dx and every step's parameter
