@@ -95,14 +95,19 @@ __global__ __launch_bounds__(64) void critic_report_kernel(const float* __restri
 // (expo_fc_fwd_slabs), added in slab order.  A block = 16 columns x G row groups (G <= 64), the groups' sums added in a
 // fixed tree through LDS (round 6: one block of 8 row groups x 128 columns walked 24 dependent rows and added the groups one
 // after the other -- 9 us for 192 rows).  G is the largest power of two that divides the real block when the real and fake
-// blocks are equally long: group g then holds real row g + i G next to fake row g + i G, whose gradients -w2 s / n and
-// +w2 s' / n cancel EXACTLY where the two slopes agree -- the bias gradient of a unit is often exactly zero, and Adam turns
-// a rounding-level residue there into a full +-lr step.
+// blocks are equally long.
+// gb1 with equally long blocks (`paired`): real row m and fake row n_real + m, whose gradients -w2 s / n and +w2 s' / n are
+// exact negatives of each other where the two slopes agree, are added TO EACH OTHER first, and group g accumulates those pair
+// sums for m = g, g + G, ...: every such pair is exactly 0 before it meets anything else, so a unit whose pairs all agree
+// gets gb1 == 0.0 for every row count -- the bias gradient of a unit is often exactly zero, and Adam turns a rounding-level
+// residue there into a full +-lr step.  (Real rows first and fake rows after would cancel only with one row per side in a
+// group; there the two orders are the same additions.)  Unequal blocks: the loss rows in index order per group.  gw2 takes
+// the loss rows in index order always.
 __global__ __launch_bounds__(1024) void critic_head_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ h,
                                                                const float* __restrict__ thpre, int th_slabs, int n_real,
-                                                               int n_fake, int n_interp, int hidden, int groups, float inv_n,
-                                                               float leak, float* __restrict__ gb1, float* __restrict__ gw2,
-                                                               float* __restrict__ gb2) {
+                                                               int n_fake, int n_interp, int hidden, int groups, int paired,
+                                                               float inv_n, float leak, float* __restrict__ gb1,
+                                                               float* __restrict__ gw2, float* __restrict__ gb2) {
   __shared__ float p1[64][17], p2[64][17];
   const int col = threadIdx.x & 15, grp = threadIdx.x >> 4;
   const int n_loss = n_real + n_fake;
@@ -112,7 +117,8 @@ __global__ __launch_bounds__(1024) void critic_head_bwd_kernel(const float* __re
   if (j < hidden && grp < groups) {
     for (int m = grp; m < n_loss; m += groups) {
       const float dl = m < n_real ? -inv_n : inv_n;
-      s1 += dh[size_t(m) * hidden + j];
+      if (!paired) s1 += dh[size_t(m) * hidden + j];
+      else if (m < n_real) s1 += dh[size_t(m) * hidden + j] + dh[size_t(n_real + m) * hidden + j];
       s2 = fmaf(dl, h[size_t(m) * hidden + j], s2);
     }
     for (int m = grp; m < n_interp; m += groups) {
@@ -245,10 +251,11 @@ int expo_critic_head_bwd(const float* dh, const float* h, const float* thpre, in
   if (th_slabs < 1 || th_slabs > 64) return fail(EXPO_E_BADARG, "critic_head_bwd: 1 <= th_slabs <= 64");
   if (!dh || !h || (n_interp > 0 && !thpre) || !gb1 || !gw2 || !gb2) return fail(EXPO_E_BADARG, "null pointer");
   int groups = 64;  // row groups per block: see the kernel
-  if (n_real > 0 && n_real == n_fake)
+  const int paired = n_real > 0 && n_real == n_fake;
+  if (paired)
     while (groups > 1 && n_real % groups != 0) groups >>= 1;
   hipLaunchKernelGGL(critic_head_bwd_kernel, dim3(unsigned((hidden + 15) / 16)), dim3(1024), 0, static_cast<hipStream_t>(stream),
-                     dh, h, thpre, th_slabs, n_real, n_fake, n_interp, hidden, groups, inv_n, leak, gb1, gw2, gb2);
+                     dh, h, thpre, th_slabs, n_real, n_fake, n_interp, hidden, groups, paired, inv_n, leak, gb1, gw2, gb2);
   HIP_TRY(hipGetLastError(), "critic_head_bwd launch");
   return EXPO_OK;
 }

@@ -838,7 +838,10 @@ int expo_conv_tuning(int tile, int nt, int slices);
  *                         (expo_adam_step with step_advanced = 1)
  *   expo_critic_head_bwd  gb1 = sum over the real + fake rows of dh;  gw2 = sum over those rows of dlogit h + sum over
  *                         the interpolated rows of thpre slope(h) (thpre float32 [th_slabs][n_interp][hidden]: the penalty's
- *                         tangent in front of fc1's activation, as partial sums like hpre);  gb2 = sum of dlogit
+ *                         tangent in front of fc1's activation, as partial sums like hpre);  gb2 = sum of dlogit.
+ *                         n_real == n_fake: gb1 adds dh[m] + dh[n_real + m] first and sums those pairs, so a unit whose
+ *                         real / fake pairs have equal slopes (dh exact negatives) gets gb1 == 0.0 exactly, for every
+ *                         row count; unequal counts: the rows in index order
  *   expo_plane_sums       sums[n][c - first] = sum over the pixels of x[n][.][c], first <= c < channels (<= 16 planes):
  *                         the gradient reaching the per-image values planes_concat broadcast (critics.py:64-76)
  *   expo_gp_direct        g = u[..., 0:3] + ds (u float32 [n][pixels][u_channels], ds [n][pixels][3]);

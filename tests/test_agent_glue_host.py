@@ -11,6 +11,7 @@ import torch
 from oracle import agent_np
 from oracle import filters_np as fnp
 from tests import _agent_glue_ref as R
+from tests._glue_checks import fd_check as _fd_check, rejected as _rejected
 
 f32, f64 = np.float32, np.float64
 
@@ -63,26 +64,6 @@ def test_heads_fwd_is_regress_packed_row_by_row(fid):
 
 
 # ---- the hand-derived gradients ----------------------------------------------------------------------------------------
-def _fd_check(loss_rows, x, analytic, name, h0=1e-4):
-  """d (per-row loss) / d x[:, c] by central differences with steps h and h / 2.  The scheme's own error estimate: the
-  truncation error of the h / 2 difference is a third of |D(h) - D(h / 2)|; its rounding error 2^-52 |loss| / (h / 2)."""
-  x = np.asarray(x, dtype=f64)
-  base = np.abs(loss_rows(x))
-  for c in range(x.shape[1]):
-    h = h0 * max(1.0, float(np.abs(x[:, c]).max()))
-    d = []
-    for step in (h, h / 2):
-      e = np.zeros_like(x)
-      e[:, c] = step
-      d.append((loss_rows(x + e) - loss_rows(x - e)) / (2 * step))
-    bound = np.abs(d[0] - d[1]) + 2.0**-50 * (base + 1e-300) / (h / 2) + 1e-300
-    err = np.abs(analytic[:, c] - d[1])
-    assert (err <= bound).all(), (name, c, float((err / bound).max()))
-    # ... and the estimate is tight enough to tell a 0.1 % error wherever the derivative is not itself negligible
-    big = np.abs(analytic[:, c]) > 1e-3 * np.abs(analytic).max()
-    assert (bound[big] <= 1e-3 * np.abs(analytic[big, c])).all(), (name, c)
-
-
 def _torch_select_loss(l, ids, gs, gq, eps, c_e, progress, k):
   sm = torch.softmax(l, dim=1)
   b = (sm + 1e-37) * (1 - eps) + eps / k
@@ -226,14 +207,6 @@ def test_params_constant_is_four_times_the_restatement_error():
 
 
 # ---- the comparisons of the GPU tests must be able to fail -------------------------------------------------------------
-def _rejected(check, got):
-  try:
-    check(got)
-  except AssertionError:
-    return True
-  return False
-
-
 def test_wrong_selection_results_are_rejected():
   k = 8
   c, x = _case(k, 10)  # n = 63, exploration 0, training mode, progress 0.3
