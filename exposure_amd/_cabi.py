@@ -88,6 +88,9 @@ SIGNATURES = {
     'expo_chain_fused_fwd_ragged_taps': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                               ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
                                               ctypes.POINTER(_vp), _vp]),
+    'expo_chain_fused_masked_fwd_ragged': (_i, [_vp, _fp, _fp, _i, _f, _f, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
+                                                ctypes.POINTER(_vp), _vp]),
     'expo_decode_workspace_bytes': (_sz, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
     'expo_decode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _fp, _i,
                                 ctypes.POINTER(_vp), _i, _vp, _sz, _vp]),
@@ -572,12 +575,9 @@ def chain_fused_fwd_taps(filter_ids, params, x, y, tap_mask, taps):
            'expo_chain_fused_fwd_taps')
 
 
-def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
-  """``chain_fused_fwd_ragged`` with taps (``expo_chain_fused_fwd_ragged_taps``): taps is a list of N contiguous device
-  tensors, taps[i] (T, H_i, W_i, 3) of one dtype (uint8 or the images' dtype, as in ``chain_fused_fwd_taps``).  ys may
-  be None (taps only); taps may be None when tap_mask is 0.  The per-image checks are as lean as the call without
-  taps."""
-  lib = load()
+def _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps):
+  """The checks the ragged calls with taps share, a few attribute reads per image: -> (steps, device, tap format, hs,
+  ws), or None for an empty list."""
   n = len(xs)
   if ys is not None and len(ys) != n:
     raise ExposureHipError('exposure_amd: xs and ys must have the same length')
@@ -590,7 +590,7 @@ def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
   _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
   t = _tap_count(tap_mask, steps)
   if n == 0:
-    return
+    return None
   dt, dev = xs[0].dtype, filter_ids.get_device()
   if params.get_device() != dev:
     raise ExposureHipError('exposure_amd: filter_ids and params must be on the images\' device')
@@ -623,12 +623,50 @@ def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
         raise ExposureHipError('exposure_amd: taps[%d] must be a contiguous device tensor (%d, %d, %d, 3) of the '
                                'dtype of taps[0]' % (i, t, h, w))
     hs[i], ws[i] = h, w
+  return steps, dev, fmt, hs, ws
+
+
+def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
+  """``chain_fused_fwd_ragged`` with taps (``expo_chain_fused_fwd_ragged_taps``): taps is a list of N contiguous device
+  tensors, taps[i] (T, H_i, W_i, 3) of one dtype (uint8 or the images' dtype, as in ``chain_fused_fwd_taps``).  ys may
+  be None (taps only); taps may be None when tap_mask is 0.  The per-image checks are as lean as the call without
+  taps."""
+  lib = load()
+  args = _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps)
+  if args is None:
+    return
+  steps, dev, fmt, hs, ws = args
+  n = len(xs)
   with torch.cuda.device(dev):
     _check(lib.expo_chain_fused_fwd_ragged_taps(_ptr(filter_ids), _ptr(params), steps, _ptr_array(xs),
                                                 None if ys is None else _ptr_array(ys), (ctypes.c_int * n)(*hs),
                                                 (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]), tap_mask, fmt,
                                                 None if taps is None else _ptr_array(taps), _stream()),
            'expo_chain_fused_fwd_ragged_taps')
+
+
+def chain_fused_masked_fwd_ragged(filter_ids, params, mask_params, xs, ys, maximum_sharpness, minimum_strength, tap_mask=0,
+                                  taps=None):
+  """``chain_fused_fwd_ragged_taps`` with the spatial mask of cfg.masking at every step
+  (``expo_chain_fused_masked_fwd_ragged``): mask_params (N, steps, 6) float32 on the images' device, row (i, k) the
+  squashed mask parameters of image i's step k (as ``apply_dispatch_fwd`` takes them).  xs, ys, tap_mask and taps as in
+  ``chain_fused_fwd_ragged_taps``, with the same per-image checks."""
+  lib = load()
+  args = _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps)
+  n = len(xs)
+  _f32(mask_params, 'mask_params', (n, filter_ids.shape[1], 6))
+  if args is None:
+    return
+  steps, dev, fmt, hs, ws = args
+  if mask_params.get_device() != dev:
+    raise ExposureHipError('exposure_amd: mask_params must be on the images\' device')
+  with torch.cuda.device(dev):
+    _check(lib.expo_chain_fused_masked_fwd_ragged(_ptr(filter_ids), _ptr(params), _ptr(mask_params), steps,
+                                                  float(maximum_sharpness), float(minimum_strength), _ptr_array(xs),
+                                                  None if ys is None else _ptr_array(ys), (ctypes.c_int * n)(*hs),
+                                                  (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]), tap_mask, fmt,
+                                                  None if taps is None else _ptr_array(taps), _stream()),
+           'expo_chain_fused_masked_fwd_ragged')
 
 
 def decode_workspace_bytes(hs, ws, channels, code_bits):

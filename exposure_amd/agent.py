@@ -326,6 +326,8 @@ class Agent(nn.Module):
         'pdf_batch': pdf,
         'params24': params24,
     }
+    if cfg.masking:
+      debug_info['mask6'] = mask6  # the selected filter's squashed mask rows: what a replay of this step needs
 
     # Calculate new states (agent.py:207-238)
     is_last_step = (torch.abs(states[:, STATE_STEP_DIM:STATE_STEP_DIM + 1] + 1 - cfg.test_steps) < 1e-4).to(

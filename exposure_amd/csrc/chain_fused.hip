@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/exposure_hip.h"
 #include "filter_math.h"
 #include "pixel_io.h"
@@ -45,50 +47,58 @@ namespace expo {
 // images of any sizes).
 // `tap(k, out)` sees the image after step k (the tap kernels below); the default does nothing and the kernels without
 // taps compile to the same code as before it existed.
+// chain_step is one step, OUT OF PLACE (in -> out), shared with the masked step loop further down.
+template <typename T>
+__device__ __forceinline__ void chain_step(int id, const float* prm, float klane, float2_lut* tab, const float* in,
+                                           float* out) {
+  constexpr int PPL = PixTraits<T>::PPL;
+#define EXPO_CASE(ID, F)                              \
+  case ID: {                                          \
+    const typename F::Prm q = F::load(prm);           \
+    _Pragma("unroll") for (int k = 0; k < PPL; ++k) F::fwd(q, in + 3 * k, out + 3 * k); \
+  } break;
+  switch (id) {
+    EXPO_CASE(0, ExposureF)
+    EXPO_CASE(1, GammaF)
+    EXPO_CASE(2, WhiteBalanceF)
+    EXPO_CASE(3, SatPlusF)
+    case 4:
+      curve_lut_build<1>(klane, tab);
+      curve_lut_map<1, PPL>(in, out, tab);
+      __builtin_amdgcn_wave_barrier();  // the next curve step of this wave rewrites the table
+      break;
+    EXPO_CASE(5, ContrastF)
+    EXPO_CASE(6, WnbF)
+    case 7:
+      curve_lut_build<3>(klane, tab);
+      curve_lut_map<3, PPL>(in, out, tab);
+      __builtin_amdgcn_wave_barrier();
+      break;
+    EXPO_CASE(8, LevelF)
+    default:  // id -1 (the all-zero one-hot selects nothing) -> the image becomes 0.  Written as arithmetic (clamp,
+      // then x * 0 + 0: exactly +0 for every input incl. inf / NaN) rather than as 24 constant moves: those the
+      // compiler executes speculatively in front of the neighbouring case (Exposure) on EVERY step.  (No
+      // __builtin_unreachable() for ids outside [-1, 8] either: with it hipcc 7.2 drops the first two values of the
+      // fp32 kernel's first pixel row -- found by the fp32 parity test, gpurun r03p17.)
+#pragma unroll
+      for (int j = 0; j < PPL * 3; ++j) out[j] = fmaf(clamp01x(in[j], -65504.0f, 65504.0f), 0.0f, 0.0f);
+      break;
+  }
+#undef EXPO_CASE
+}
+
 struct NoTap { __device__ void operator()(int, const float*) const {} };
 template <typename T, class Tap = NoTap>
 __device__ inline void chain_fused_run(const int32_t* idn, const float* prn,
                                                 int steps, float2_lut* tab, int plane, float* v,
                                                 const Tap& tap = Tap()) {
   constexpr int PPL = PixTraits<T>::PPL;
-  // One step, OUT OF PLACE (in -> out).  The step loop below runs two steps per trip with the two pixel arrays (and
-  // the two parameter sets) swapping roles, so no loop-carried value is ever copied: the rolled one-step loop paid 24
-  // v_mov + 24 s_mov per step for its loop PHIs (the coupled filters cannot update a pixel in place), ~17 % of the
-  // instructions a wave issued for an 8-step sequence.
+  // The step loop below runs two steps per trip with the two pixel arrays (and the two parameter sets) swapping
+  // roles, so no loop-carried value is ever copied: the rolled one-step loop paid 24 v_mov + 24 s_mov per step for its
+  // loop PHIs (the coupled filters cannot update a pixel in place), ~17 % of the instructions a wave issued for an
+  // 8-step sequence.
   auto apply = [&](int id, const float* prm, float klane, const float* in, float* out) {
-#define EXPO_CASE(ID, F)                              \
-  case ID: {                                          \
-    const typename F::Prm q = F::load(prm);           \
-    _Pragma("unroll") for (int k = 0; k < PPL; ++k) F::fwd(q, in + 3 * k, out + 3 * k); \
-  } break;
-    switch (id) {
-      EXPO_CASE(0, ExposureF)
-      EXPO_CASE(1, GammaF)
-      EXPO_CASE(2, WhiteBalanceF)
-      EXPO_CASE(3, SatPlusF)
-      case 4:
-        curve_lut_build<1>(klane, tab);
-        curve_lut_map<1, PPL>(in, out, tab);
-        __builtin_amdgcn_wave_barrier();  // the next curve step of this wave rewrites the table
-        break;
-      EXPO_CASE(5, ContrastF)
-      EXPO_CASE(6, WnbF)
-      case 7:
-        curve_lut_build<3>(klane, tab);
-        curve_lut_map<3, PPL>(in, out, tab);
-        __builtin_amdgcn_wave_barrier();
-        break;
-      EXPO_CASE(8, LevelF)
-      default:  // id -1 (the all-zero one-hot selects nothing) -> the image becomes 0.  Written as arithmetic (clamp,
-        // then x * 0 + 0: exactly +0 for every input incl. inf / NaN) rather than as 24 constant moves: those the
-        // compiler executes speculatively in front of the neighbouring case (Exposure) on EVERY step.  (No
-        // __builtin_unreachable() for ids outside [-1, 8] either: with it hipcc 7.2 drops the first two values of the
-        // fp32 kernel's first pixel row -- found by the fp32 parity test, gpurun r03p17.)
-#pragma unroll
-        for (int j = 0; j < PPL * 3; ++j) out[j] = fmaf(clamp01x(in[j], -65504.0f, 65504.0f), 0.0f, 0.0f);
-        break;
-    }
-#undef EXPO_CASE
+    chain_step<T>(id, prm, klane, tab, in, out);
   };
   // software-pipelined parameter fetch: a step's id and 24 parameters (wave-uniform -> scalar loads into SGPRs)
   // are requested one step ahead, hiding the scalar-load latency; `k*` is a per-lane copy (lane l <-> parameter l)
@@ -551,6 +561,227 @@ static int chain_fused_fwd_ragged_taps_t(const int32_t* ids, const float* params
 // kernel arguments of the ragged tap kernel: ids, params, steps, tap_mask, the table
 static_assert(sizeof(RaggedTapTable<half_t>) + 32 <= 4096, "the ragged tap table must fit the 4 KB kernarg block");
 
+// ------------------------------------------------------- masked: the fused pass with cfg.masking on
+// Filter.apply with the spatial mask of filters.py:110-148 at every step, fused like the pass above: the mask of a
+// pixel needs its (row, column), the luminance of the running value -- what the previous step left in registers -- and
+// six per-image numbers per step, so nothing keeps the steps from running back to back on a pixel group.
+//   v_{k+1} = fma(m, process(v_k) - v_k, v_k),  m = MaskPrm(mask_params[i][k], ...).eval_rc(row, col, v_k).m
+// (the masked lerp of apply_fwd_body, exposure_hip.hip); id -1 makes the image +0 without a mask.
+// Coordinates: a group's first (row, column) is found once per group and kept (2 VGPRs); every step re-walks the
+// group's other pixels from it with PixelWalk (a few integer operations per pixel, held in step with the pixel
+// arithmetic by its ordering anchor) instead of carrying 2 * PPL grid values through the step loop.
+// Mask constants: the six numbers of a step are wave-uniform and are fetched one step ahead, with the id and the
+// parameters; the image's geometry (grid constants, the walk's steps) is set up once per wave in `geo`.
+constexpr int kTapNone = -1;  // FMT of the masked kernels without taps (EXPO_TAP_STORAGE / EXPO_TAP_U8 otherwise)
+struct NoSink { __device__ __forceinline__ void operator()(int, int, int, const float*) const {} };
+
+// `geo` with the coefficients of one step's six mask parameters (MaskPrm::load's own arithmetic; its geometry part
+// is constant-folded away here)
+__device__ __forceinline__ MaskPrm mask_step(MaskPrm geo, const float* mp, float sharp, float min_strength) {
+  const MaskPrm s = MaskPrm::load(mp, sharp, min_strength, 1, 1);
+  geo.a = s.a; geo.b = s.b; geo.c = s.c; geo.d2 = s.d2; geo.k = s.k; geo.S = s.S;
+  return geo;
+}
+
+// chain_fused_run with the mask: mpn[steps][6] the image's mask rows, (row0, col0) the group's first pixel
+template <typename T, bool VEC, class Tap>
+__device__ inline void chain_fused_masked_run(const int32_t* idn, const float* prn, const float* mpn, int steps,
+                                              const MaskPrm& geo, float sharp, float min_strength, int row0, int col0,
+                                              float2_lut* tab, int plane, float* v, const Tap& tap) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  // one step, out of place; `masked` is uniform: false for id -1 (the image is +0, whatever the mask) and for the
+  // padding half-trip, which therefore stays Exposure with 0 EV alone, x * 2^0 = x exactly for every value
+  auto apply = [&](int id, bool masked, const float* prm, const float* mp, float klane, const float* in, float* out) {
+    chain_step<T>(id, prm, klane, tab, in, out);
+    if (masked) {
+      const MaskPrm mk = mask_step(geo, mp, sharp, min_strength);
+      int row = row0, col = col0;
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) {
+        if (k > 0) mk.pw.step(pixel_step_is_b<T, VEC>(k), row, col);
+        const float m = mk.eval_rc(row, col, in + 3 * k).m;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[3 * k + c] = fmaf(m, out[3 * k + c] - in[3 * k + c], in[3 * k + c]);
+        PixelWalk::after(row, col, out[3 * k]);
+      }
+    }
+  };
+  float pa[EXPO_MAX_PARAMS], pb[EXPO_MAX_PARAMS], qa[6], qb[6];
+  float ka = 0.f, kb = 0.f;
+  int ia = 0, ib = 0;
+  bool ma = false, mb = false;
+  auto fetch = [&](int st, float* p, float* q, float& kl, int& id, bool& masked) {
+    const bool live = st < steps;
+    const int sn = live ? st : steps - 1;  // (past the end: any valid row)
+    id = live ? idn[sn] : 0;
+    masked = live && id >= 0;
+    kl = prn[sn * EXPO_MAX_PARAMS + plane];
+#pragma unroll
+    for (int j = 0; j < EXPO_MAX_PARAMS; ++j) p[j] = prn[sn * EXPO_MAX_PARAMS + j];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) q[j] = mpn[sn * 6 + j];
+    if (!live) p[0] = 0.0f;
+  };
+  if (steps <= 0) return;
+  float a[PPL * 3], w[PPL * 3];  // (locals, copied in and out: see chain_fused_run)
+#pragma unroll
+  for (int j = 0; j < PPL * 3; ++j) a[j] = v[j];
+  fetch(0, pa, qa, ka, ia, ma);
+#pragma unroll 1
+  for (int st = 0; st < steps; st += 2) {
+    fetch(st + 1, pb, qb, kb, ib, mb);
+    apply(ia, ma, pa, qa, ka, a, w);
+    tap(st, w);
+    fetch(st + 2, pa, qa, ka, ia, ma);
+    apply(ib, mb, pb, qb, kb, w, a);
+    tap(st + 1, a);  // (st + 1 == steps: the identity half-trip, never a tap)
+  }
+#pragma unroll
+  for (int j = 0; j < PPL * 3; ++j) v[j] = a[j];
+}
+
+// one image's share of the grid, with or without taps (Sink = NoSink); yi may be NULL with taps
+template <typename T, bool VEC, class IO, class Sink>
+__device__ __forceinline__ void chain_fused_masked_image(const int32_t* idn, const float* prn, const float* mpn,
+                                                         int steps, float sharp, float min_strength, const T* xi, T* yi,
+                                                         int h, int w, int first_gw, int stride, float2_lut* tab,
+                                                         const Sink& sink) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int hw = h * w, groups = (hw + PPL - 1) / PPL;
+  const int lane = threadIdx.x & 63;
+  const int plane = lane % EXPO_MAX_PARAMS;
+  const float none[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const MaskPrm geo = MaskPrm::load(none, sharp, min_strength, h, w, pixel_step_a<T, VEC>(), pixel_step_b<T, VEC>());
+  auto run = [&](float* v, int g, int gw) {
+    int row0, col0;
+    geo.pw.start(pixel_index<T, VEC>(g, 0, lane), row0, col0);
+    chain_fused_masked_run<T, VEC>(idn, prn, mpn, steps, geo, sharp, min_strength, row0, col0, tab, plane, v,
+                                   [&](int k, const float* o) { sink(k, gw, lane, o); });
+  };
+  if constexpr (VEC) {
+#if EXPO_FP16_OVFL
+    // the fp16 stores (y and storage taps) saturate as in stream_groups, which sets this only when it stores itself
+    if constexpr (sizeof(T) == 2) __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);
+#endif
+    const T* const ins[1] = {xi};
+    const __amdgpu_buffer_rsrc_t ry = make_image_rsrc(yi, hw);
+    stream_groups<T, 1, false, false, IO>(ins, nullptr, hw, first_gw, stride, [&](float (&v)[1][PPL * 3], int g) {
+      const int gw = g - lane;
+      run(v[0], g, gw);
+      if (yi) store_raw<IO::kStore>(ry, chunk_byte_offset<T>(gw, lane), pack<T>(v[0]));
+    });
+  } else {
+    for (int g0 = first_gw; g0 < groups; g0 += stride) {  // wave-uniform trip count, as chain_fused_image
+      const int g = g0 + lane;
+      float v[PPL * 3];
+      load_slow<T>(xi, g, hw, v);
+      run(v, g, g0);
+      if (yi) store_slow<T>(yi, g, hw, v);
+    }
+  }
+}
+
+// the ragged table with each image's height and width (the mask's grid) and its tap buffer
+template <typename T>
+struct MaskedRaggedTable {
+  const T* x[kRaggedMaxImages];
+  T* y[kRaggedMaxImages];
+  char* taps[kRaggedMaxImages];
+  int h[kRaggedMaxImages], w[kRaggedMaxImages];
+  int first[kRaggedMaxImages + 1];
+  int n;
+  uint64_t vec;
+};
+// kernel arguments: ids, params, mask_params, steps, sharp, min_strength, tap_mask, the table
+static_assert(sizeof(MaskedRaggedTable<half_t>) + 48 <= 4096, "the masked ragged table must fit the 4 KB kernarg block");
+
+template <typename T, class IO, bool ANY_SLOW, int FMT>
+__global__ __launch_bounds__(kThreads) void chain_fused_masked_ragged_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ params, const float* __restrict__ mask_params, int steps,
+    float sharp, float min_strength, uint64_t tap_mask, const MaskedRaggedTable<T> tab) {
+  __shared__ float2_lut curve_tab[kWaves][32];
+  __shared__ __attribute__((aligned(4))) uint8_t tap_stage[kWaves][TapStage<T, FMT>::kBytes];
+  const int b = blockIdx.x;
+  int lo = 0, hi = tab.n - 1;  // the last image whose first block is <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab.first[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int i = __builtin_amdgcn_readfirstlane(lo);
+  const int h = tab.h[i], w = tab.w[i];
+  const int first_gw = (b - tab.first[i]) * kThreads + (threadIdx.x & ~63);
+  const int stride = (tab.first[i + 1] - tab.first[i]) * kThreads;
+  const int32_t* idn = ids + size_t(i) * steps;
+  const float* prn = params + size_t(i) * steps * EXPO_MAX_PARAMS;
+  const float* mpn = mask_params + size_t(i) * steps * 6;
+  float2_lut* const lut = curve_tab[threadIdx.x >> 6];
+  auto image = [&](auto vec) {
+    constexpr bool VEC = decltype(vec)::value;
+    if constexpr (FMT == kTapNone) {
+      chain_fused_masked_image<T, VEC, IO>(idn, prn, mpn, steps, sharp, min_strength, tab.x[i], tab.y[i], h, w,
+                                           first_gw, stride, lut, NoSink());
+    } else {
+      using Sink = TapSink<T, VEC, IO, FMT>;
+      const Sink sink{tab.taps[i], size_t(h) * w * 3 * Sink::ES, tap_mask, h * w, tap_stage[threadIdx.x >> 6]};
+      chain_fused_masked_image<T, VEC, IO>(idn, prn, mpn, steps, sharp, min_strength, tab.x[i], tab.y[i], h, w,
+                                           first_gw, stride, lut, sink);
+    }
+  };
+  if (!ANY_SLOW || ((tab.vec >> i) & 1)) image(std::true_type());
+  else image(std::false_type());
+}
+
+// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output
+template <typename T, int FMT>
+static int chain_fused_masked_ragged_t(const int32_t* ids, const float* params, const float* mask_params, int steps,
+                                       float sharp, float min_strength, const void* const* xs, void* const* ys,
+                                       const int* hs, const int* ws, int n, uint64_t tap_mask, void* const* taps,
+                                       hipStream_t s) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  long bytes = 0;
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kRaggedMaxImages) {
+    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
+    MaskedRaggedTable<T> tab = {};
+    tab.n = m;
+    bool any_slow = false;
+    long blocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      tab.x[j] = static_cast<const T*>(xs[i]);
+      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+      tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
+      tab.h[j] = hs[i];
+      tab.w[j] = ws[i];
+      tab.first[j] = int(blocks);
+      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
+      const uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
+                          (FMT == EXPO_TAP_STORAGE ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
+      const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
+      if (vec) tab.vec |= uint64_t(1) << j;
+      any_slow = any_slow || !vec;
+    }
+    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    tab.first[m] = int(blocks);
+    const int32_t* idb = ids + size_t(base) * steps;
+    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
+    const float* mpb = mask_params + size_t(base) * steps * 6;
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
+    if (stream && any_slow)
+      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoStream, true, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
+    else if (stream)
+      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoStream, false, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
+    else if (any_slow)
+      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoCached, true, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
+    else
+      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoCached, false, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
+    HIP_TRY(hipGetLastError(), "chain_fused_masked_fwd_ragged launch");
+  }
+  return EXPO_OK;
+}
+
 static int check_taps(int steps, uint64_t tap_mask, int tap_format) {
   if (tap_format != EXPO_TAP_STORAGE && tap_format != EXPO_TAP_U8)
     return fail(EXPO_E_BADARG, "tap_format must be EXPO_TAP_STORAGE or EXPO_TAP_U8");
@@ -640,6 +871,35 @@ int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* par
                : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
   return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
              : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
+}
+
+int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* params, const float* mask_params,
+                                       int steps, float maximum_sharpness, float minimum_strength,
+                                       const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
+                                       int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
+  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
+  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
+  if (n == 0) return EXPO_OK;
+  if (!xs || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params || !mask_params)))
+    return fail(EXPO_E_BADARG, "null pointer");
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
+    if (!xs[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
+    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float sh = maximum_sharpness, ms = minimum_strength;
+#define EXPO_MASKED(T, FMT) \
+  chain_fused_masked_ragged_t<T, FMT>(filter_ids, params, mask_params, steps, sh, ms, xs, ys, hs, ws, n, tap_mask, taps, s)
+  const bool f16 = dtype == EXPO_F16;
+  if (!tap_mask) return f16 ? EXPO_MASKED(half_t, kTapNone) : EXPO_MASKED(float, kTapNone);
+  if (tap_format == EXPO_TAP_U8) return f16 ? EXPO_MASKED(half_t, EXPO_TAP_U8) : EXPO_MASKED(float, EXPO_TAP_U8);
+  return f16 ? EXPO_MASKED(half_t, EXPO_TAP_STORAGE) : EXPO_MASKED(float, EXPO_TAP_STORAGE);
+#undef EXPO_MASKED
 }
 
 }  // extern "C"

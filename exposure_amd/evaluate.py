@@ -118,12 +118,43 @@ def fused_chain_ragged_taps(images, filter_ids, params24, tap_mask, tap_dtype, o
   return ys, taps
 
 
+def fused_masked_chain(high_res, filter_ids, params24, mask6, cfg, tap_mask=0, tap_dtype=None, out=True):
+  """``fused_chain_taps`` with the spatial masks of ``cfg.masking`` (``expo_chain_fused_masked_fwd_ragged``): mask6
+  (N, steps, 6) are the squashed mask rows the agent recorded (``debug_info['mask6']``).  The dense tensor goes in as N
+  views of one ragged call; the taps come back as a (T, N, H, W, 3) view of an image-major buffer."""
+  from . import _cabi
+  x = high_res.contiguous()
+  n, t = x.shape[0], bin(tap_mask).count('1')
+  y = torch.empty_like(x) if out else None
+  taps = torch.empty((n, t) + tuple(x.shape[1:]), dtype=tap_dtype or x.dtype, device=x.device)
+  _cabi.chain_fused_masked_fwd_ragged(filter_ids.contiguous().to(torch.int32), params24.contiguous().float(),
+                                      mask6.contiguous().float(), list(x.unbind(0)),
+                                      list(y.unbind(0)) if out else None, float(cfg.maximum_sharpness),
+                                      float(cfg.minimum_strength), tap_mask, list(taps.unbind(0)) if t else None)
+  return y, taps.transpose(0, 1)
+
+
+def fused_masked_chain_ragged(images, filter_ids, params24, mask6, cfg, tap_mask=0, tap_dtype=None, out=True):
+  """``fused_chain_ragged_taps`` with the spatial masks of ``cfg.masking``: (outs or None, per image a (T, H_i, W_i, 3)
+  tensor of ``tap_dtype``), one ragged launch per 64 images."""
+  from . import _cabi
+  xs = [im.contiguous() for im in images]
+  ys = [torch.empty_like(x) for x in xs] if out else None
+  t = bin(tap_mask).count('1')
+  taps = [torch.empty((t,) + tuple(x.shape[-3:]), dtype=tap_dtype or x.dtype, device=x.device) for x in xs]
+  _cabi.chain_fused_masked_fwd_ragged(filter_ids.contiguous().to(torch.int32), params24.contiguous().float(),
+                                      mask6.contiguous().float(), xs, ys, float(cfg.maximum_sharpness),
+                                      float(cfg.minimum_strength), tap_mask, taps if t else None)
+  return ys, taps
+
+
 def encode_u8(img):
   """``save_png``'s 8-bit encoding on the device: saturate(round_half_even(float(img) * 255))."""
   return torch.round(img.float() * 255.0).clamp_(0, 255).to(torch.uint8)
 
 
 INTERMEDIATES = (None, 'u8', 'storage')
+MASKS = ('stepwise', 'fused')
 
 
 def _intermediate_mask(stops):
@@ -131,11 +162,12 @@ def _intermediate_mask(stops):
   return sum(1 << i for i, stopped in enumerate(stops) if not stopped)
 
 
-def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, keep_hi=False):
+def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, keep_hi=False, mask6=None):
   """The agent loop of ``retouch`` on the (N, 64, 64, 3) proxies: ``steps`` steps (or until every image stopped), the
   full-resolution tensor ``hi`` filtered at every step when given (the reference's schedule).  Returns low, states,
   hi, and per step the selected ids, the C-ABI ids, the (N, 24) parameter rows, whether every image was stopped after
-  it and (``keep_hi``) the full-resolution tensor after it."""
+  it and (``keep_hi``) the full-resolution tensor after it.  ``mask6``: a list that receives every step's (N, 6)
+  squashed mask rows when the agent reports them (``cfg.masking``)."""
   cfg = agent.cfg
   n, dev = low.shape[0], low.device
   states = torch.zeros((n, cfg.num_state_dim), dtype=torch.float32, device=dev)  # get_initial_states
@@ -154,6 +186,8 @@ def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, ke
       abi_ids.append(dbg['abi_filter_ids'])
       params.append(dbg['params24'])
     trace.append(dbg['selected_filter_ids'].clone())
+    if mask6 is not None and 'mask6' in dbg:
+      mask6.append(dbg['mask6'])
     if keep_hi:
       his.append(hi)
     stops.append(bool((states[:, STATE_STOPPED_DIM] > 0).all()))
@@ -162,10 +196,13 @@ def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, ke
   return low, states, hi, trace, abi_ids, params, stops, his
 
 
-def _trace_result(out, low, states, trace, abi_ids, params, return_trace):
+def _trace_result(out, low, states, trace, abi_ids, params, return_trace, mask6=()):
   if return_trace == 'full':  # the per-step operations (what net.py:825-877 pickles as decisions / operations)
-    return out, low, states, dict(selected=torch.stack(trace, dim=1), abi_filter_ids=torch.stack(abi_ids, dim=1),
-                                  params24=torch.stack(params, dim=1))
+    ops = dict(selected=torch.stack(trace, dim=1), abi_filter_ids=torch.stack(abi_ids, dim=1),
+               params24=torch.stack(params, dim=1))
+    if mask6:  # cfg.masking: the (N, S, 6) squashed mask rows of the selected filters
+      ops['mask6'] = torch.stack(mask6, dim=1)
+    return out, low, states, ops
   if return_trace:
     return out, low, states, torch.stack(trace, dim=1)
   return out, low, states
@@ -173,7 +210,7 @@ def _trace_result(out, low, states, trace, abi_ids, params, return_trace):
 
 @torch.no_grad()
 def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trace=False, fused=True,
-            intermediates=None, proxy='torch', picture=False):
+            intermediates=None, proxy='torch', picture=False, masks='stepwise'):
   """Run the 5-step retouching loop.  ``high_res``: NHWC device tensor (fp16/fp32), linear RGB.
   Returns (retouched_high_res, retouched_low_res, states[, trace of selected filter ids][, intermediates]).
 
@@ -191,14 +228,22 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   ``proxy='device'`` makes the 64x64 proxies with ``make_low_res_batch`` (one HIP launch) instead of torch's
   interpolate; ``'torch'`` (default) is ``make_low_res``.  ``picture=True`` appends the (N, H, W, 3) uint8 picture of
   the result (``save_png``'s encoding) as the last entry: on the fused path an EXPO_TAP_U8 tap of the last executed
-  step, written by the pass that writes the output; otherwise ``encode_u8`` of it."""
+  step, written by the pass that writes the output; otherwise ``encode_u8`` of it.
+
+  ``masks`` matters with ``cfg.masking`` only.  ``'stepwise'`` (default): the reference's schedule, as ``fused=False``.
+  ``'fused'``: the spatial mask of a step needs the pixel's position, the running value's luminance and six numbers the
+  agent regresses on the proxy, so the fused pass takes it too (``fused_masked_chain``): the agent runs on the proxies
+  only, and intermediates, picture and trace come as on the unmasked fused path.  fp32 between steps instead of one
+  storage rounding per step.  ``fused=False`` wins over it."""
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
   if proxy not in PROXIES:
     raise ValueError('proxy must be one of %s' % (PROXIES,))
-  if cfg.masking:
-    fused = False  # the spatial mask depends on the running image: no parameters-only replay
+  if masks not in MASKS:
+    raise ValueError('masks must be one of %s' % (MASKS,))
+  if cfg.masking and masks != 'fused':
+    fused = False  # the reference's schedule: every step filters the full-resolution tensor
   generic = any(f.uses_generic_kernels() for f in agent.filters)
   if generic:
     fused = False  # cfg.curve_steps != 8: the one-pass kernel is instantiated for 8-step curves (reference schedule instead)
@@ -212,22 +257,30 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   if z is None:
     z = torch.rand((n, cfg.z_dim), device=dev)
   hi = high_res.contiguous()
+  mask6 = []
   low, states, stepped, trace, abi_ids, params, stops, his = _agent_steps(
       agent, low, z, steps, dropout_masks, hi=None if fused else hi, generic=generic,
-      keep_hi=bool(intermediates) and not fused)
+      keep_hi=bool(intermediates) and not fused, mask6=mask6)
   mask = _intermediate_mask(stops)
   inter = pic = None
   last = 1 << (len(stops) - 1)  # the last executed step: its u8 tap is the picture of the output
+  if fused and cfg.masking:  # the same pass with the spatial masks
+    def chain_taps(x, ids, prm, tap_mask, tap_dtype):
+      return fused_masked_chain(x, ids, prm, torch.stack(mask6, dim=1), cfg, tap_mask, tap_dtype)
+  else:
+    chain_taps = fused_chain_taps
   if fused and picture and intermediates != 'storage':
     # one pass: the output, the picture and (u8) the intermediates, which are the taps before the last
-    hi, taps = fused_chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1),
-                                (mask if intermediates else 0) | last, torch.uint8)
+    hi, taps = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1),
+                          (mask if intermediates else 0) | last, torch.uint8)
     pic = taps[-1]
     if intermediates:
       inter = taps if mask & last else taps[:-1]
   elif fused and intermediates:
-    hi, inter = fused_chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), mask,
-                                 torch.uint8 if intermediates == 'u8' else hi.dtype)
+    hi, inter = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), mask,
+                           torch.uint8 if intermediates == 'u8' else hi.dtype)
+  elif fused and cfg.masking:
+    hi, _ = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), 0, None)
   elif fused:
     hi = fused_chain(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1))
   else:
@@ -239,13 +292,13 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
         inter = encode_u8(inter)
   if picture and pic is None:
     pic = encode_u8(hi)
-  res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace)
+  res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace, mask6)
   return res + ((inter,) if intermediates else ()) + ((pic,) if picture else ())
 
 
 @torch.no_grad()
 def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False, intermediates=None,
-                  proxy='torch', picture=False):
+                  proxy='torch', picture=False, masks='stepwise'):
   """``retouch`` over a list of images of ANY sizes at once (the batching ``evaluate.py:18`` asks for, without its
   same-resolution restriction).  ``images``: N device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype and device.
   One 64x64 proxy per image (``make_low_res``) is stacked, the agent runs once on the (N, 64, 64, 3) stack, and the
@@ -261,12 +314,17 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
   ``intermediates`` as in ``retouch`` appends a list of N (S-1, H_i, W_i, 3) tensors; on the fused path they come from
   the ragged launch itself (``fused_chain_ragged_taps``).  ``proxy`` and ``picture`` as in ``retouch``: ``'device'``
   builds all N proxies in one launch (``make_low_res_batch``) instead of ``make_low_res`` per image, and
-  ``picture=True`` appends a list of N (H_i, W_i, 3) uint8 pictures, from the ragged launch that writes the outputs."""
+  ``picture=True`` appends a list of N (H_i, W_i, 3) uint8 pictures, from the ragged launch that writes the outputs.
+
+  ``masks='fused'`` with ``cfg.masking`` keeps the batch together as without masks: one agent call on the stacked
+  proxies, then ``fused_masked_chain_ragged`` (see ``retouch``); the default ``'stepwise'`` runs every image alone."""
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
   if proxy not in PROXIES:
     raise ValueError('proxy must be one of %s' % (PROXIES,))
+  if masks not in MASKS:
+    raise ValueError('masks must be one of %s' % (MASKS,))
   images = list(images)
   n = len(images)
   if n == 0:
@@ -281,12 +339,12 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     z = torch.rand((n, cfg.z_dim), device=dev)
   hi4 = [im if im.dim() == 4 else im[None] for im in images]
   generic = any(f.uses_generic_kernels() for f in agent.filters)
-  if cfg.masking or generic:  # no parameters-only replay: per image, the schedule retouch picks for it
+  if (cfg.masking and masks != 'fused') or generic:  # per image, the schedule retouch picks for it
     rows = []
     for i, im in enumerate(hi4):
-      masks = None if dropout_masks is None else [tuple(m[i:i + 1] for m in step) for step in dropout_masks]
-      rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=masks, return_trace=return_trace or True,
-                          intermediates=intermediates, proxy=proxy, picture=picture))
+      drop = None if dropout_masks is None else [tuple(m[i:i + 1] for m in step) for step in dropout_masks]
+      rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=drop, return_trace=return_trace or True,
+                          intermediates=intermediates, proxy=proxy, picture=picture, masks=masks))
     outs = [r[0].reshape(im.shape) for r, im in zip(rows, images)]
     low, states = torch.cat([r[1] for r in rows]), torch.cat([r[2] for r in rows])
     extra = ([r[4][:, 0] for r in rows],) if intermediates else ()
@@ -301,26 +359,32 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     low = make_low_res_batch(images, cfg.source_img_size)
   else:
     low = torch.cat([make_low_res(im, cfg.source_img_size) for im in hi4])
-  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks)
+  mask6 = []
+  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks, mask6=mask6)
   ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
+  if cfg.masking:  # the same launches with the spatial masks
+    def ragged_taps(xs, ids, prm, tap_mask, tap_dtype):
+      return fused_masked_chain_ragged(xs, ids, prm, torch.stack(mask6, dim=1), cfg, tap_mask, tap_dtype)
+  else:
+    ragged_taps = fused_chain_ragged_taps
   if picture and intermediates != 'storage':
     # one ragged launch: the outputs, the pictures and (u8) the intermediates, which are the taps before the last
     mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
-    outs, taps = fused_chain_ragged_taps(images, ids, prm, (mask if intermediates else 0) | last, torch.uint8)
-    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+    outs, taps = ragged_taps(images, ids, prm, (mask if intermediates else 0) | last, torch.uint8)
+    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
     if intermediates:
       res += ([t if mask & last else t[:-1] for t in taps],)
     return res + ([t[-1] for t in taps],)
   if picture:  # storage intermediates: the taps of a launch have one format, so the pictures are encoded from the outputs
-    outs, inter = fused_chain_ragged_taps(images, ids, prm, _intermediate_mask(stops), images[0].dtype)
-    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+    outs, inter = ragged_taps(images, ids, prm, _intermediate_mask(stops), images[0].dtype)
+    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
     return res + (inter, [encode_u8(o.reshape(o.shape[-3:])) for o in outs])
   if not intermediates:
-    outs = fused_chain_ragged(images, ids, prm)
-    return _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
-  outs, inter = fused_chain_ragged_taps(images, ids, prm, _intermediate_mask(stops),
+    outs = ragged_taps(images, ids, prm, 0, None)[0] if cfg.masking else fused_chain_ragged(images, ids, prm)
+    return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
+  outs, inter = ragged_taps(images, ids, prm, _intermediate_mask(stops),
                                         torch.uint8 if intermediates == 'u8' else images[0].dtype)
-  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace) + (inter,)
+  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6) + (inter,)
 
 
 def load_image(path):
@@ -500,6 +564,12 @@ def main(argv=None):
   ap.add_argument('--seed', type=int, default=None, help='seeds the random-init weights / dropout / noise')
   ap.add_argument('--stepwise', action='store_true', help="the reference's schedule: filter the full-resolution "
                   'tensor at every step instead of one fused pass at the end')
+  ap.add_argument('--masking', action='store_true',
+                  help="cfg.masking: every filter acts through the reference's spatial mask (filters.py:110-148); the "
+                  "heads' shapes do not depend on it.  The reference's schedule unless --fused-masks is given")
+  ap.add_argument('--fused-masks', action='store_true',
+                  help='with --masking: apply the masked steps in the one fused pass (fp32 between steps, taps, --batch '
+                  'in one ragged launch) instead of step by step.  --stepwise wins over it')
   ap.add_argument('--batch', type=int, default=1, metavar='N',
                   help='retouch up to N images at once, of any sizes, grouped in argument order (retouch_batch: the '
                   'agent runs on the stacked proxies, one ragged launch applies the filters).  z and the dropout '
@@ -533,6 +603,8 @@ def main(argv=None):
   if args.filters:
     flt = [getattr(F, FILTER_BY_SHORT_NAME[name.strip()]) for name in args.filters.split(',')]
   cfg = make_cfg(filters=flt)
+  if args.masking:
+    cfg.masking = True
   agent = Agent(cfg).to(dev)
   if args.weights and args.tf_checkpoint:
     ap.error('--weights and --tf-checkpoint are alternatives')
@@ -550,6 +622,7 @@ def main(argv=None):
     args.png = True
   proxy = 'device' if args.device_proxy else 'torch'
   inter_kind = 'u8' if args.step_by_step else None
+  masks = 'fused' if args.fused_masks else 'stepwise'
   records = []
   pictures = []  # --score: every emitted image's uint8 picture, kept on the device (not the float outputs)
 
@@ -592,7 +665,7 @@ def main(argv=None):
     for path in args.images:
       hi, = load_group([path])
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
-                    picture=args.device_png)
+                    picture=args.device_png, masks=masks)
       emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None,
            res[-1][0] if args.device_png else None)
   else:
@@ -600,7 +673,7 @@ def main(argv=None):
       paths = args.images[b:b + args.batch]
       his = load_group(paths)
       res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
-                          picture=args.device_png)
+                          picture=args.device_png, masks=masks)
       outs, states, ops = res[0], res[2], res[3]
       for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
         emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,

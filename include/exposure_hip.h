@@ -56,7 +56,7 @@ extern "C" {
                               (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
                               9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged,
                               expo_area_resize_ragged, expo_pack_recut, expo_bilinear_resize_ragged,
-                              expo_patch_stats, expo_stat_hist */
+                              expo_patch_stats, expo_stat_hist, expo_chain_fused_masked_fwd_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -349,6 +349,27 @@ int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, in
 int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* params, int steps,
                                      const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                      int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
+
+/*
+ * The fused inference pass with the reference's spatial masks (cfg.masking, filters.py:110-148): an added export of
+ * ABI 9 (the version is unchanged), modelled on expo_chain_fused_fwd_ragged_taps.  For image i, v_0 = float(x_i) and
+ * for k = 0 .. steps-1, per pixel (row, col):
+ *   id -1:      v_{k+1} = +0
+ *   otherwise:  m = the mask of expo_filter_apply_dispatch_fwd for mask_params[i][k] at (row, col) with the luminance
+ *               of v_k, on the grid of an hs[i] x ws[i] image;  v_{k+1} = fma(m, process_id(v_k) - v_k, v_k) per channel
+ * fp32 between steps, one rounding to storage at the end (the per-step schedule rounds after every step).
+ *   mask_params  device float32 [n][steps][6]: tanh_range(-5, 5)(raw) of the step's selected filter, as
+ *                expo_filter_apply_dispatch_fwd takes them; maximum_sharpness / minimum_strength as there
+ *   tap_mask, tap_format, taps, ys NULL: exactly as expo_chain_fused_fwd_ragged_taps (tap_mask 0: no taps, taps may
+ *                be NULL)
+ * Launches, the per-image choice of the dwordx3 path, the cache policy and the validation are those of
+ * expo_chain_fused_fwd_ragged_taps, plus mask_params non-NULL when steps > 0.  Every output is bit-identical to the
+ * same image passed alone.
+ */
+int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* params, const float* mask_params,
+                                       int steps, float maximum_sharpness, float minimum_strength,
+                                       const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
+                                       int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
 
 /*
  * Decode: the integer codes of n input images, as the file holds them, to the linear storage tensors that
