@@ -22,6 +22,7 @@ EXPO_CURVE_MAX_STEPS = 16
 EXPO_F16, EXPO_F32 = 0, 1
 EXPO_MAX_PARAMS = 24
 EXPO_TAP_STORAGE, EXPO_TAP_U8 = 0, 1
+EXPO_TAP_U16 = 3
 NUM_PARAMS = (1, 1, 3, 1, 8, 1, 1, 24, 2)  # ids 0..7 = cfg.filters order, 8 = LevelFilter
 
 # every symbol include/exposure_hip.h declares: name -> (restype, argtypes)
@@ -530,12 +531,15 @@ def chain_fused_fwd_ragged(filter_ids, params, xs, ys):
 
 
 def _tap_format(taps, dt):
-  """EXPO_TAP_U8 for uint8 tap tensors, EXPO_TAP_STORAGE for taps of the images' dtype"""
+  """EXPO_TAP_U8 for uint8 tap tensors, EXPO_TAP_U16 for uint16 ones, EXPO_TAP_STORAGE for taps of the images' dtype"""
   if taps.dtype is torch.uint8:
     return EXPO_TAP_U8
+  if taps.dtype is torch.uint16:
+    return EXPO_TAP_U16
   if taps.dtype is dt:
     return EXPO_TAP_STORAGE
-  raise ExposureHipError('exposure_amd: taps must be uint8 or of the images\' dtype %s, got %s' % (dt, taps.dtype))
+  raise ExposureHipError('exposure_amd: taps must be uint8, uint16 or of the images\' dtype %s, got %s'
+                         % (dt, taps.dtype))
 
 
 def _tap_count(tap_mask, steps):
@@ -548,8 +552,8 @@ def _tap_count(tap_mask, steps):
 def chain_fused_fwd_taps(filter_ids, params, x, y, tap_mask, taps):
   """``chain_fused_fwd`` that also writes the image after every step k whose bit is set in tap_mask
   (``expo_chain_fused_fwd_taps``).  taps: (T, N, H, W, 3) contiguous device tensor, T = popcount(tap_mask), tap j the
-  j-th set bit; uint8 -> the 8-bit PNG values (EXPO_TAP_U8), x's dtype -> the storage values (EXPO_TAP_STORAGE).  y may
-  be None (taps only); taps may be None when tap_mask is 0."""
+  j-th set bit; uint8 -> the 8-bit PNG values (EXPO_TAP_U8), uint16 -> the 16-bit TIFF values (EXPO_TAP_U16), x's dtype ->
+  the storage values (EXPO_TAP_STORAGE).  y may be None (taps only); taps may be None when tap_mask is 0."""
   lib = load()
   _img(x, 'x')
   if y is not None:
@@ -628,7 +632,7 @@ def _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps):
 
 def chain_fused_fwd_ragged_taps(filter_ids, params, xs, ys, tap_mask, taps):
   """``chain_fused_fwd_ragged`` with taps (``expo_chain_fused_fwd_ragged_taps``): taps is a list of N contiguous device
-  tensors, taps[i] (T, H_i, W_i, 3) of one dtype (uint8 or the images' dtype, as in ``chain_fused_fwd_taps``).  ys may
+  tensors, taps[i] (T, H_i, W_i, 3) of one dtype (uint8, uint16 or the images' dtype, as in ``chain_fused_fwd_taps``).  ys may
   be None (taps only); taps may be None when tap_mask is 0.  The per-image checks are as lean as the call without
   taps."""
   lib = load()

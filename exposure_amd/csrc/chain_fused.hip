@@ -254,21 +254,46 @@ __global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd
 //   they are staged in a per-wave LDS buffer (the wave's chunk as one contiguous 1536 / 768-byte run) and leave as
 //   coalesced buffer_store_dword; a dword that is not 4-byte aligned or straddles the plane's end goes out as four
 //   bounds-checked buffer_store_byte instead (exact, slower).  The element-wise path stores bytes.
+//   EXPO_TAP_U16: as U8 with 65535 and little-endian shorts, 6 B/px; a plane may start at any 2-byte boundary.
+//   fp32 storage: a lane's pixel per input vector is 6 bytes -- staged like U8 (1536 bytes per wave); a dword that is
+//   misaligned (plane base 2 mod 4: every odd-sized plane of a dense tap tensor but the first) or straddles the plane's
+//   end leaves as two bounds-checked buffer_store_short.  fp16 storage: a lane's two pixels per input vector are 12
+//   bytes at exactly the storage tap's byte positions, so the codes leave as dwordx3 like EXPO_TAP_STORAGE, no
+//   staging; the host side then puts the plane's base into the image's alignment test (tap_vector_store), and an
+//   image whose plane is only 2-byte aligned takes the element-wise path, which stores shorts.
 template <typename T>
 __device__ __forceinline__ float tap_u8_level(float v) {
   const float s = float(T(v));  // rounded to the storage dtype (saturating like pack<T>; either way -> 255)
   return __builtin_amdgcn_fmed3f(__builtin_rintf(s * 255.0f), 0.0f, 255.0f);
 }
 
+template <typename T>
+__device__ __forceinline__ float tap_u16_level(float v) {
+  const float s = float(T(v));  // as tap_u8_level; one fp32 multiply, round half even, clamp
+  return __builtin_amdgcn_fmed3f(__builtin_rintf(s * 65535.0f), 0.0f, 65535.0f);
+}
+template <typename T>
+__device__ __forceinline__ uint32_t tap_u16_pair(float lo, float hi) {  // two codes, little-endian in one dword
+  return uint32_t(tap_u16_level<T>(lo)) | (uint32_t(tap_u16_level<T>(hi)) << 16);
+}
+
+// bytes per channel value of a tap plane
+template <typename T, int FMT>
+constexpr int tap_elem_bytes() { return FMT == EXPO_TAP_U8 ? 1 : FMT == EXPO_TAP_U16 ? 2 : int(sizeof(T)); }
+// the vector path writes the plane with the dwordx3 stores of y: its base must be 4-byte aligned like y's
+template <typename T, int FMT>
+constexpr bool tap_vector_store() { return FMT == EXPO_TAP_STORAGE || (FMT == EXPO_TAP_U16 && sizeof(T) == 2); }
+
 template <typename T, bool VEC, class IO, int FMT>
 struct TapSink {
-  static constexpr int ES = FMT == EXPO_TAP_U8 ? 1 : int(sizeof(T));  // bytes per channel value of a plane
-  static constexpr int BPR = 3 * VecTraits<T>::PPV;                    // u8 bytes per lane and 12-byte input vector
+  static constexpr int ES = tap_elem_bytes<T, FMT>();
+  static constexpr int VPR = 3 * VecTraits<T>::PPV;  // values per lane and 12-byte input vector (a lane's row)
+  static constexpr int BPR = VPR * ES;               // their bytes in a u8 / u16 plane
   char* base;        // plane 0 of this image
   size_t stride;     // bytes from plane j to plane j + 1
   uint64_t mask;
   int hw;
-  uint8_t* stage;    // this wave's 4 * 64 * BPR bytes of LDS (u8 vector path)
+  uint8_t* stage;    // this wave's 4 * 64 * BPR bytes of LDS (u8 vector path, u16 vector path of fp32 storage)
 
   // store the values v (the group of lane `lane`, starting at wave chunk gw; element-wise path: group g = gw + lane)
   __device__ __forceinline__ void operator()(int k, int gw, int lane, const float* v) const {
@@ -279,6 +304,16 @@ struct TapSink {
     if constexpr (!VEC) {
       if constexpr (FMT == EXPO_TAP_STORAGE) {
         store_slow<T>(reinterpret_cast<T*>(plane), gw + lane, hw, v);
+      } else if constexpr (FMT == EXPO_TAP_U16) {
+        uint16_t* const p = reinterpret_cast<uint16_t*>(plane);
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+          const int px = (gw + lane) * PPL + q;
+          if (px < hw) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[size_t(px) * 3 + c] = uint16_t(uint32_t(tap_u16_level<T>(v[q * 3 + c])));
+          }
+        }
       } else {
         uint8_t* const p = reinterpret_cast<uint8_t*>(plane);
 #pragma unroll
@@ -292,14 +327,29 @@ struct TapSink {
       }
     } else if constexpr (FMT == EXPO_TAP_STORAGE) {
       store_raw<IO::kStore>(make_image_rsrc(reinterpret_cast<T*>(plane), hw), chunk_byte_offset<T>(gw, lane), pack<T>(v));
+    } else if constexpr (FMT == EXPO_TAP_U16 && sizeof(T) == 2) {
+      // two bytes per value like the storage tap: the same byte positions, the same stores (4-byte aligned plane)
+      RawGroup r;
+#pragma unroll
+      for (int row = 0; row < 4; ++row) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) r.q[row][e] = tap_u16_pair<T>(v[row * 6 + e * 2], v[row * 6 + e * 2 + 1]);
+      }
+      store_raw<IO::kStore>(make_image_rsrc(reinterpret_cast<T*>(plane), hw), chunk_byte_offset<T>(gw, lane), r);
     } else {
-      const int nbytes = hw * 3;
+      const int nbytes = hw * 3 * ES;
       const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(plane, 0, nbytes, kBufferRsrcFlags);
-      // v holds 4 input vectors (rows of the chunk, 64 * BPR bytes apart in the plane), BPR values each in memory order
+      // v holds 4 input vectors (rows of the chunk, 64 * BPR bytes apart in the plane), VPR values each in memory order
 #pragma unroll
       for (int row = 0; row < 4; ++row) {
         uint8_t* const dst = stage + row * 64 * BPR + lane * BPR;
-        if constexpr (BPR % 2 == 0) {
+        if constexpr (FMT == EXPO_TAP_U16) {  // (fp32 storage: 3 shorts, 2-byte aligned in the stage)
+#pragma unroll
+          for (int e = 0; e < VPR; ++e) {
+            const uint16_t h = uint16_t(uint32_t(tap_u16_level<T>(v[row * VPR + e])));
+            __builtin_memcpy(dst + 2 * e, &h, 2);
+          }
+        } else if constexpr (BPR % 2 == 0) {
 #pragma unroll
           for (int e = 0; e < BPR; e += 2) {
             uint32_t u = __builtin_amdgcn_cvt_pk_u8_f32(tap_u8_level<T>(v[row * BPR + e]), 0, 0);
@@ -314,7 +364,7 @@ struct TapSink {
       }
       __builtin_amdgcn_wave_barrier();  // one wave: its LDS operations execute in order
       const bool aligned = (reinterpret_cast<uintptr_t>(plane) & 3) == 0;
-      const int chunk = gw * PPL * 3;  // the chunk's first byte in the plane
+      const int chunk = gw * PPL * 3 * ES;  // the chunk's first byte in the plane
 #pragma unroll
       for (int q = 0; q < BPR; ++q) {  // 4 * 64 * BPR bytes = BPR dwords per lane
         uint32_t d;
@@ -322,6 +372,9 @@ struct TapSink {
         const int o = chunk + (q * 64 + lane) * 4;
         if (aligned && o + 4 <= nbytes) {
           __builtin_amdgcn_raw_buffer_store_b32(d, r, o, 0, IO::kStore);
+        } else if constexpr (FMT == EXPO_TAP_U16) {  // a short past the plane's end is dropped by the bounds check
+          __builtin_amdgcn_raw_buffer_store_b16(uint16_t(d), r, o, 0, IO::kStore);
+          __builtin_amdgcn_raw_buffer_store_b16(uint16_t(d >> 16), r, o + 2, 0, IO::kStore);
         } else {  // bytes past the plane's end are dropped by the buffer's bounds check
 #pragma unroll
           for (int b = 0; b < 4; ++b) __builtin_amdgcn_raw_buffer_store_b8(uint8_t(d >> (8 * b)), r, o + b, 0, IO::kStore);
@@ -334,7 +387,9 @@ struct TapSink {
 
 template <typename T, int FMT>
 struct TapStage {
-  static constexpr int kBytes = FMT == EXPO_TAP_U8 ? 4 * 64 * 3 * VecTraits<T>::PPV : 4;
+  // the formats staged on the vector path: 4 rows x 64 lanes x a lane's bytes per row (TapSink::BPR)
+  static constexpr bool kStaged = FMT == EXPO_TAP_U8 || (FMT == EXPO_TAP_U16 && sizeof(T) == 4);
+  static constexpr int kBytes = kStaged ? 4 * 64 * 3 * VecTraits<T>::PPV * tap_elem_bytes<T, FMT>() : 4;
 };
 
 // chain_fused_image with taps; yi may be NULL (taps only)
@@ -493,8 +548,9 @@ static int chain_fused_fwd_ragged_t(const int32_t* ids, const float* params, int
 template <typename T, int FMT>
 static int chain_fused_fwd_taps_t(const int32_t* ids, const float* params, int steps, const void* x, void* y, int n,
                                   int h, int w, uint64_t tap_mask, void* taps, hipStream_t s) {
-  // a storage tap plane is stored like y (dwordx3): its base joins the alignment test; u8 planes handle any base
-  Geom g = make_geom<T>(n, h, w, {x, y, FMT == EXPO_TAP_STORAGE ? taps : nullptr}, kGeomMap);
+  // a storage tap plane is stored like y (dwordx3), and so is a u16 plane of fp16 storage: its base joins the
+  // alignment test; u8 planes and the u16 planes of fp32 storage handle any base
+  Geom g = make_geom<T>(n, h, w, {x, y, tap_vector_store<T, FMT>() ? taps : nullptr}, kGeomMap);
   g.blocks_x = (g.groups + kThreads - 1) / kThreads;
   const dim3 grid(g.blocks_x, n), block(kThreads);
   const T* xt = static_cast<const T*>(x);
@@ -535,7 +591,7 @@ static int chain_fused_fwd_ragged_taps_t(const int32_t* ids, const float* params
       tab.first[j] = int(blocks);
       blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
       const uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
-                          (FMT == EXPO_TAP_STORAGE ? reinterpret_cast<uintptr_t>(taps[i]) : 0);
+                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(taps[i]) : 0);
       const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
       if (vec) tab.vec |= uint64_t(1) << j;
       any_slow = any_slow || !vec;
@@ -572,7 +628,7 @@ static_assert(sizeof(RaggedTapTable<half_t>) + 32 <= 4096, "the ragged tap table
 // arithmetic by its ordering anchor) instead of carrying 2 * PPL grid values through the step loop.
 // Mask constants: the six numbers of a step are wave-uniform and are fetched one step ahead, with the id and the
 // parameters; the image's geometry (grid constants, the walk's steps) is set up once per wave in `geo`.
-constexpr int kTapNone = -1;  // FMT of the masked kernels without taps (EXPO_TAP_STORAGE / EXPO_TAP_U8 otherwise)
+constexpr int kTapNone = -1;  // FMT of the masked kernels without taps (an EXPO_TAP_* format otherwise)
 struct NoSink { __device__ __forceinline__ void operator()(int, int, int, const float*) const {} };
 
 // `geo` with the coefficients of one step's six mask parameters (MaskPrm::load's own arithmetic; its geometry part
@@ -758,7 +814,7 @@ static int chain_fused_masked_ragged_t(const int32_t* ids, const float* params, 
       tab.first[j] = int(blocks);
       blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
       const uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
-                          (FMT == EXPO_TAP_STORAGE ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
+                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
       const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
       if (vec) tab.vec |= uint64_t(1) << j;
       any_slow = any_slow || !vec;
@@ -783,8 +839,8 @@ static int chain_fused_masked_ragged_t(const int32_t* ids, const float* params, 
 }
 
 static int check_taps(int steps, uint64_t tap_mask, int tap_format) {
-  if (tap_format != EXPO_TAP_STORAGE && tap_format != EXPO_TAP_U8)
-    return fail(EXPO_E_BADARG, "tap_format must be EXPO_TAP_STORAGE or EXPO_TAP_U8");
+  if (tap_format != EXPO_TAP_STORAGE && tap_format != EXPO_TAP_U8 && tap_format != EXPO_TAP_U16)
+    return fail(EXPO_E_BADARG, "tap_format must be EXPO_TAP_STORAGE, EXPO_TAP_U8 or EXPO_TAP_U16");
   if (steps < 64 && (tap_mask >> steps) != 0) return fail(EXPO_E_BADARG, "tap_mask has a bit >= steps");
   return EXPO_OK;
 }
@@ -840,6 +896,9 @@ int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, in
   if (tap_format == EXPO_TAP_U8)
     return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_U8>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
                : chain_fused_fwd_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
+  if (tap_format == EXPO_TAP_U16)
+    return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_U16>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
+               : chain_fused_fwd_taps_t<float, EXPO_TAP_U16>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
   return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
              : chain_fused_fwd_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
 }
@@ -869,6 +928,9 @@ int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* par
   if (tap_format == EXPO_TAP_U8)
     return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
                : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
+  if (tap_format == EXPO_TAP_U16)
+    return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_U16>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
+               : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_U16>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
   return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
              : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
 }
@@ -898,6 +960,7 @@ int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* p
   const bool f16 = dtype == EXPO_F16;
   if (!tap_mask) return f16 ? EXPO_MASKED(half_t, kTapNone) : EXPO_MASKED(float, kTapNone);
   if (tap_format == EXPO_TAP_U8) return f16 ? EXPO_MASKED(half_t, EXPO_TAP_U8) : EXPO_MASKED(float, EXPO_TAP_U8);
+  if (tap_format == EXPO_TAP_U16) return f16 ? EXPO_MASKED(half_t, EXPO_TAP_U16) : EXPO_MASKED(float, EXPO_TAP_U16);
   return f16 ? EXPO_MASKED(half_t, EXPO_TAP_STORAGE) : EXPO_MASKED(float, EXPO_TAP_STORAGE);
 #undef EXPO_MASKED
 }

@@ -11,6 +11,7 @@ Image decoding (16-bit TIFF / ProPhoto linearisation, ``util.py:311-323, 495-501
 outputs of ``net.py:825-877`` the CLI writes the linear result (.npy) and, with ``--png``, the reference's 8-bit
 ``retouched`` / ``input_tone_mapped`` pictures; with ``--step-by-step`` also the ``intermediateNN`` pictures of
 ``net.py:820-823`` (``evaluate.py:31``); the debug pickle and the cv2-drawn ``steps`` panel are out of scope.
+``--tiff16`` writes the pictures as 16-bit TIFFs instead, the depth the input files have.
 """
 import warnings
 
@@ -94,7 +95,7 @@ def fused_chain_ragged(images, filter_ids, params24):
 def fused_chain_taps(high_res, filter_ids, params24, tap_mask, tap_dtype, out=True):
   """``fused_chain`` that also returns the image after every step k whose bit is set in ``tap_mask``, from the same
   pass (``expo_chain_fused_fwd_taps``): (out or None, taps (T, N, H, W, 3) of ``tap_dtype``: torch.uint8 for the 8-bit
-  PNG values, else high_res's dtype)."""
+  PNG values, torch.uint16 for the 16-bit TIFF values, else high_res's dtype)."""
   from . import _cabi
   x = high_res.contiguous()
   y = torch.empty_like(x) if out else None
@@ -153,8 +154,32 @@ def encode_u8(img):
   return torch.round(img.float() * 255.0).clamp_(0, 255).to(torch.uint8)
 
 
-INTERMEDIATES = (None, 'u8', 'storage')
+def encode_u16(img):
+  """The 16-bit encoding of ``--tiff16`` on the device: saturate(round_half_even(float(img) * 65535)), what an
+  EXPO_TAP_U16 tap holds.  The codes leave as the low halves of int32 values: a float -> uint16 cast is not relied on."""
+  codes = torch.round(img.float() * 65535.0).clamp_(0, 65535).to(torch.int32).contiguous()
+  return codes.view(torch.int16)[..., ::2].contiguous().view(torch.uint16)  # (little-endian host and device)
+
+
+INTERMEDIATES = (None, 'u8', 'u16', 'storage')
+PICTURES = (False, True, 'u8', 'u16')
 MASKS = ('stepwise', 'fused')
+_CODE_DTYPES = {'u8': torch.uint8, 'u16': torch.uint16}
+_ENCODERS = {'u8': encode_u8, 'u16': encode_u16}
+
+
+def _picture_kind(picture, intermediates):
+  """``picture=`` as None / 'u8' / 'u16' (True is 'u8').  The taps of a launch share one format, and so do the pictures
+  of a call: 'u8' and 'u16' do not mix."""
+  if isinstance(picture, str):
+    if picture not in _CODE_DTYPES:
+      raise ValueError('picture must be one of %s' % (PICTURES,))
+    kind = picture
+  else:
+    kind = 'u8' if picture else None
+  if kind and intermediates in _CODE_DTYPES and intermediates != kind:
+    raise ValueError('picture=%r and intermediates=%r: one call makes pictures of one depth' % (picture, intermediates))
+  return kind
 
 
 def _intermediate_mask(stops):
@@ -214,9 +239,9 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   """Run the 5-step retouching loop.  ``high_res``: NHWC device tensor (fp16/fp32), linear RGB.
   Returns (retouched_high_res, retouched_low_res, states[, trace of selected filter ids][, intermediates]).
 
-  ``intermediates='u8'`` / ``'storage'`` adds the step-by-step pictures of ``net.py:820-823``: a (S-1, N, H, W, 3)
-  tensor (with the shipped agent every step but the last; in general every step after which the images were not
-  stopped), uint8 ``save_png`` values or the storage dtype.  On the fused path they come from the same pass
+  ``intermediates='u8'`` / ``'u16'`` / ``'storage'`` adds the step-by-step pictures of ``net.py:820-823``: a
+  (S-1, N, H, W, 3) tensor (with the shipped agent every step but the last; in general every step after which the
+  images were not stopped), uint8 ``save_png`` values, uint16 ``encode_u16`` values or the storage dtype.  On the fused path they come from the same pass
   (``fused_chain_taps``); otherwise they are the per-step tensors, encoded on the device.
 
   ``fused=True`` (default): the agent steps run on the 64x64 proxy only, recording each step's
@@ -228,7 +253,9 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   ``proxy='device'`` makes the 64x64 proxies with ``make_low_res_batch`` (one HIP launch) instead of torch's
   interpolate; ``'torch'`` (default) is ``make_low_res``.  ``picture=True`` appends the (N, H, W, 3) uint8 picture of
   the result (``save_png``'s encoding) as the last entry: on the fused path an EXPO_TAP_U8 tap of the last executed
-  step, written by the pass that writes the output; otherwise ``encode_u8`` of it.
+  step, written by the pass that writes the output; otherwise ``encode_u8`` of it.  ``picture='u8'`` is the same;
+  ``picture='u16'`` makes it the uint16 picture (EXPO_TAP_U16 / ``encode_u16``: with fp16 storage it carries fp16's 11
+  significant bits, the full 16-bit depth needs fp32 storage).  'u8' and 'u16' do not mix in one call (``ValueError``).
 
   ``masks`` matters with ``cfg.masking`` only.  ``'stepwise'`` (default): the reference's schedule, as ``fused=False``.
   ``'fused'``: the spatial mask of a step needs the pixel's position, the running value's luminance and six numbers the
@@ -242,6 +269,7 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
     raise ValueError('proxy must be one of %s' % (PROXIES,))
   if masks not in MASKS:
     raise ValueError('masks must be one of %s' % (MASKS,))
+  kind = _picture_kind(picture, intermediates)
   if cfg.masking and masks != 'fused':
     fused = False  # the reference's schedule: every step filters the full-resolution tensor
   generic = any(f.uses_generic_kernels() for f in agent.filters)
@@ -263,22 +291,22 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
       keep_hi=bool(intermediates) and not fused, mask6=mask6)
   mask = _intermediate_mask(stops)
   inter = pic = None
-  last = 1 << (len(stops) - 1)  # the last executed step: its u8 tap is the picture of the output
+  last = 1 << (len(stops) - 1)  # the last executed step: its u8 / u16 tap is the picture of the output
   if fused and cfg.masking:  # the same pass with the spatial masks
     def chain_taps(x, ids, prm, tap_mask, tap_dtype):
       return fused_masked_chain(x, ids, prm, torch.stack(mask6, dim=1), cfg, tap_mask, tap_dtype)
   else:
     chain_taps = fused_chain_taps
-  if fused and picture and intermediates != 'storage':
-    # one pass: the output, the picture and (u8) the intermediates, which are the taps before the last
+  if fused and kind and intermediates != 'storage':
+    # one pass: the output, the picture and (u8 / u16) the intermediates, which are the taps before the last
     hi, taps = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1),
-                          (mask if intermediates else 0) | last, torch.uint8)
+                          (mask if intermediates else 0) | last, _CODE_DTYPES[kind])
     pic = taps[-1]
     if intermediates:
       inter = taps if mask & last else taps[:-1]
   elif fused and intermediates:
     hi, inter = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), mask,
-                           torch.uint8 if intermediates == 'u8' else hi.dtype)
+                           _CODE_DTYPES.get(intermediates, hi.dtype))
   elif fused and cfg.masking:
     hi, _ = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), 0, None)
   elif fused:
@@ -288,12 +316,12 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
     if intermediates:
       kept = [h for i, h in enumerate(his) if (mask >> i) & 1]
       inter = torch.stack(kept) if kept else torch.empty((0,) + tuple(hi.shape), dtype=hi.dtype, device=hi.device)
-      if intermediates == 'u8':
-        inter = encode_u8(inter)
-  if picture and pic is None:
-    pic = encode_u8(hi)
+      if intermediates in _ENCODERS:
+        inter = _ENCODERS[intermediates](inter)
+  if kind and pic is None:
+    pic = _ENCODERS[kind](hi)
   res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace, mask6)
-  return res + ((inter,) if intermediates else ()) + ((pic,) if picture else ())
+  return res + ((inter,) if intermediates else ()) + ((pic,) if kind else ())
 
 
 @torch.no_grad()
@@ -314,7 +342,8 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
   ``intermediates`` as in ``retouch`` appends a list of N (S-1, H_i, W_i, 3) tensors; on the fused path they come from
   the ragged launch itself (``fused_chain_ragged_taps``).  ``proxy`` and ``picture`` as in ``retouch``: ``'device'``
   builds all N proxies in one launch (``make_low_res_batch``) instead of ``make_low_res`` per image, and
-  ``picture=True`` appends a list of N (H_i, W_i, 3) uint8 pictures, from the ragged launch that writes the outputs.
+  ``picture=True`` appends a list of N (H_i, W_i, 3) uint8 pictures, from the ragged launch that writes the outputs
+  (``'u16'``: uint16 pictures).
 
   ``masks='fused'`` with ``cfg.masking`` keeps the batch together as without masks: one agent call on the stacked
   proxies, then ``fused_masked_chain_ragged`` (see ``retouch``); the default ``'stepwise'`` runs every image alone."""
@@ -325,6 +354,7 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     raise ValueError('proxy must be one of %s' % (PROXIES,))
   if masks not in MASKS:
     raise ValueError('masks must be one of %s' % (MASKS,))
+  kind = _picture_kind(picture, intermediates)
   images = list(images)
   n = len(images)
   if n == 0:
@@ -348,7 +378,7 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     outs = [r[0].reshape(im.shape) for r, im in zip(rows, images)]
     low, states = torch.cat([r[1] for r in rows]), torch.cat([r[2] for r in rows])
     extra = ([r[4][:, 0] for r in rows],) if intermediates else ()
-    if picture:
+    if kind:
       extra += ([r[-1][0] for r in rows],)
     if return_trace == 'full':
       return (outs, low, states, {k: torch.cat([r[3][k] for r in rows]) for k in rows[0][3]}) + extra
@@ -367,23 +397,23 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
       return fused_masked_chain_ragged(xs, ids, prm, torch.stack(mask6, dim=1), cfg, tap_mask, tap_dtype)
   else:
     ragged_taps = fused_chain_ragged_taps
-  if picture and intermediates != 'storage':
-    # one ragged launch: the outputs, the pictures and (u8) the intermediates, which are the taps before the last
+  if kind and intermediates != 'storage':
+    # one ragged launch: the outputs, the pictures and (u8 / u16) the intermediates, which are the taps before the last
     mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
-    outs, taps = ragged_taps(images, ids, prm, (mask if intermediates else 0) | last, torch.uint8)
+    outs, taps = ragged_taps(images, ids, prm, (mask if intermediates else 0) | last, _CODE_DTYPES[kind])
     res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
     if intermediates:
       res += ([t if mask & last else t[:-1] for t in taps],)
     return res + ([t[-1] for t in taps],)
-  if picture:  # storage intermediates: the taps of a launch have one format, so the pictures are encoded from the outputs
+  if kind:  # storage intermediates: the taps of a launch have one format, so the pictures are encoded from the outputs
     outs, inter = ragged_taps(images, ids, prm, _intermediate_mask(stops), images[0].dtype)
     res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
-    return res + (inter, [encode_u8(o.reshape(o.shape[-3:])) for o in outs])
+    return res + (inter, [_ENCODERS[kind](o.reshape(o.shape[-3:])) for o in outs])
   if not intermediates:
     outs = ragged_taps(images, ids, prm, 0, None)[0] if cfg.masking else fused_chain_ragged(images, ids, prm)
     return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
   outs, inter = ragged_taps(images, ids, prm, _intermediate_mask(stops),
-                                        torch.uint8 if intermediates == 'u8' else images[0].dtype)
+                            _CODE_DTYPES.get(intermediates, images[0].dtype))
   return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6) + (inter,)
 
 
@@ -500,6 +530,22 @@ def save_png_u8(path, img_u8):
   return path
 
 
+def save_tiff_u16(path, img_u16):
+  """An (H, W, 3) uint16 array (``encode_u16``, or an EXPO_TAP_U16 tap) as an uncompressed 16-bit RGB TIFF: the file's
+  payload is the array byte for byte."""
+  from .tiff16 import write_tiff
+  write_tiff(path, np.ascontiguousarray(img_u16, dtype=np.uint16))
+  return path
+
+
+def _host_codes(t):
+  """A uint8 / uint16 device tensor as a NumPy array (uint16 crosses as int16: the copy of a strided view then needs
+  no uint16 kernel of torch)."""
+  if t.dtype is torch.uint16:
+    return t.view(torch.int16).cpu().numpy().view(np.uint16)
+  return t.cpu().numpy()
+
+
 def tone_mapped_input(linear):
   """``net.py:822-823``: max to white, then gamma 1/2.4 -- the ``input_tone_mapped`` picture of ``GAN.eval``.  Host
   maths also with ``--device-png``: a device ``pow`` cannot be made bit-identical to numpy's."""
@@ -587,6 +633,13 @@ def main(argv=None):
                   help='write <output>.png from 8-bit values made on the GPU: on the fused paths a tap of the last step '
                   'from the pass that writes the output, with --stepwise an encode of the result.  The same pixels as '
                   '--png, which it implies; --show-input\'s picture keeps its host maths')
+  ap.add_argument('--tiff16', action='store_true',
+                  help='write the pictures as 16-bit RGB TIFFs (uncompressed, little-endian) instead of 8-bit PNGs: '
+                  '<output>.tif and, with --step-by-step, <output>.intermediateNN.tif, code = round(value * 65535) '
+                  'saturated.  On the fused paths the codes are taps of the pass that writes the output, with --stepwise '
+                  'an encode of the results.  With --dtype f16 a value is rounded to fp16 storage first, so the picture '
+                  "carries fp16's 11 significant bits: the full 16-bit depth needs --dtype f32.  Not with --png, "
+                  '--device-png or --score (8-bit pictures: one pass makes one kind); --show-input keeps its 8-bit PNG')
   ap.add_argument('--score', default=None, metavar='TARGET_DIR',
                   help="after the run, score the retouched pictures against the 8-bit pictures of TARGET_DIR with the "
                   "paper's metric (histogram intersection of luminance, contrast and saturation, exposure_amd.metrics) "
@@ -616,19 +669,25 @@ def main(argv=None):
   dt = torch.float16 if args.dtype == 'f16' else torch.float32
   if args.batch < 1:
     ap.error('--batch must be >= 1')
+  if args.tiff16 and (args.png or args.device_png or args.score):
+    ap.error('--tiff16 does not go with --png, --device-png or --score: they need the 8-bit pictures, and one pass '
+             'makes pictures of one depth')
   if args.score:
     args.device_png = True
-  if args.step_by_step or args.device_png:
+  if (args.step_by_step and not args.tiff16) or args.device_png:
     args.png = True
   proxy = 'device' if args.device_proxy else 'torch'
-  inter_kind = 'u8' if args.step_by_step else None
+  code = 'u16' if args.tiff16 else 'u8'
+  inter_kind = code if args.step_by_step else None
+  picture = 'u16' if args.tiff16 else args.device_png  # the pictures retouch makes on the device
   masks = 'fused' if args.fused_masks else 'stepwise'
   records = []
   pictures = []  # --score: every emitted image's uint8 picture, kept on the device (not the float outputs)
 
   def emit(path, hi, out, states, ops, inter=None, pic=None):
     """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows; inter: its
-    (S-1, H, W, 3) uint8 intermediates with --step-by-step; pic: its (H, W, 3) uint8 picture with --device-png)"""
+    (S-1, H, W, 3) uint8 / uint16 intermediates with --step-by-step; pic: its (H, W, 3) uint8 picture with
+    --device-png, uint16 with --tiff16)"""
     trace = ops['selected']
     names = [agent.filters[int(j)].get_short_name() for j in trace[0]]
     print('%s: %dx%d  filters: %s' % (path, hi.shape[2], hi.shape[1], ' '.join(names)))
@@ -637,9 +696,16 @@ def main(argv=None):
     np.save(dst, result)
     if args.score:
       pictures.append(pic.contiguous())
-    pngs = {}
+    pngs, tiffs = {}, {}
+    stem = dst[:-4] if dst.endswith('.npy') else dst
+    if args.tiff16:
+      tiffs['retouched'] = save_tiff_u16(stem + '.tif', _host_codes(pic))
+      if args.show_input:
+        pngs['input_tone_mapped'] = save_png(stem + '.input_tone_mapped.png', tone_mapped_input(hi[0].float().cpu().numpy()))
+      if inter is not None:
+        for i, a in enumerate(_host_codes(inter)):
+          tiffs['intermediate%02d' % i] = save_tiff_u16('%s.intermediate%02d.tif' % (stem, i), a)
     if args.png:
-      stem = dst[:-4] if dst.endswith('.npy') else dst
       if pic is not None:
         pngs['retouched'] = save_png_u8(stem + '.png', pic.cpu().numpy())
       else:
@@ -649,7 +715,7 @@ def main(argv=None):
       if inter is not None:
         for i, a in enumerate(inter.cpu().numpy()):
           pngs['intermediate%02d' % i] = save_png_u8('%s.intermediate%02d.png' % (stem, i), a)
-    records.append(dict(image=path, output=dst, png=pngs, filters=names, states=states[0].cpu().tolist(),
+    records.append(dict(image=path, output=dst, png=pngs, tiff=tiffs, filters=names, states=states[0].cpu().tolist(),
                         abi_filter_ids=ops['abi_filter_ids'][0].cpu().tolist(),
                         params24=ops['params24'][0].cpu().numpy()))
 
@@ -665,19 +731,19 @@ def main(argv=None):
     for path in args.images:
       hi, = load_group([path])
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
-                    picture=args.device_png, masks=masks)
+                    picture=picture, masks=masks)
       emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None,
-           res[-1][0] if args.device_png else None)
+           res[-1][0] if picture else None)
   else:
     for b in range(0, len(args.images), args.batch):
       paths = args.images[b:b + args.batch]
       his = load_group(paths)
       res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
-                          picture=args.device_png, masks=masks)
+                          picture=picture, masks=masks)
       outs, states, ops = res[0], res[2], res[3]
       for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
         emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
-             res[-1][i] if args.device_png else None)
+             res[-1][i] if picture else None)
   if args.score:
     import random
     from . import metrics

@@ -71,7 +71,9 @@ def read_tiff16(path):
 
 
 def write_tiff(path, img):
-  """Minimal uncompressed little-endian writer (tests / examples)."""
+  """Uncompressed little-endian writer: one strip, chunky samples, 8 or 16 bits.  ``python -m exposure_amd.evaluate
+  --tiff16`` writes its pictures with it: the strip is ``img`` byte for byte (an EXPO_TAP_U16 plane as it left the GPU),
+  and ``read_tiff`` reads the file back."""
   img = np.ascontiguousarray(img)
   assert img.ndim == 3 and img.dtype in (np.uint8, np.uint16)
   h, w, c = img.shape

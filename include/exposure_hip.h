@@ -333,16 +333,23 @@ int expo_chain_fused_fwd_ragged(const int32_t* filter_ids, const float* params, 
  *               EXPO_TAP_U8: uint8 = saturate_[0,255](round_half_even(float(s) * 255.0f)), s the value rounded to the
  *               storage dtype first: the reference's 8-bit PNG value (cv2.imwrite(img * 255), net.py:769-772).  A NaN
  *               pixel gives an unspecified byte, as everywhere on the inference path.
+ *               EXPO_TAP_U16: uint16 = saturate_[0,65535](round_half_even(float(s) * 65535.0f)), s as for U8: one IEEE
+ *               fp32 multiply, then the rounding, then the clamp.  Little-endian, 6 B/px: a plane is byte for byte the
+ *               payload of an uncompressed 16-bit RGB TIFF.  With EXPO_F16 storage s has fp16's 11 significant bits, so
+ *               the picture has them too; the full 16-bit depth needs EXPO_F32 storage.
  *   taps        dense: ONE device buffer [T][N][H][W][3], tap-major; ragged: a HOST array of n device buffers,
- *               image i's [T][hs[i]][ws[i]][3].  A uint8 plane may start at any byte.
+ *               image i's [T][hs[i]][ws[i]][3].  A uint8 plane may start at any byte, a uint16 plane at any 2-byte
+ *               boundary (EXPO_F16 storage: a plane that is not 4-byte aligned sends its image down the element-wise
+ *               path, as an unaligned x or y does).
  *   y / ys      may be NULL (only taps are written: the 8-bit preview writes 3 B/px instead of the image's 6 B/px);
  *               ys may be NULL as a whole array, not per image.
  * Validated before anything is enqueued: as the calls without taps, plus tap_mask bits < steps, tap_format one of the
- * two, taps (and every taps[i]) non-NULL when tap_mask != 0, and y / ys NULL with tap_mask == 0 is EXPO_E_BADARG
+ * three, taps (and every taps[i]) non-NULL when tap_mask != 0, and y / ys NULL with tap_mask == 0 is EXPO_E_BADARG
  * ("nothing to write").  tap_mask == 0 with y / ys given is exactly the call without taps.
  */
 #define EXPO_TAP_STORAGE 0
 #define EXPO_TAP_U8 1
+#define EXPO_TAP_U16 3
 int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, int steps, const void* x, void* y,
                               int n, int h, int w, int dtype, uint64_t tap_mask, int tap_format, void* taps,
                               void* stream);

@@ -4,11 +4,15 @@ chosen steps.  16 x 512x512 fp16, the 8-step sequence of bench.py's chain (one f
   (a) no taps (expo_chain_fused_fwd);                     (b) 7 U8 taps + y;
   (c) 7 U8 taps, y NULL;                                  (d) 7 storage (fp16) taps + y;
   (e) today's way to the same pictures: 8 per-step expo_filter_fwd launches, each followed by the torch u8 encode;
-  (f) one 24 MP image (4000x6000), 5 steps, 4 U8 taps + y, against the same call without taps.
+  (f) one 24 MP image (4000x6000), 5 steps, 4 U8 taps + y, against the same call without taps;
+  (g) 7 U16 taps + y;                                     (h) the picture only: a U16 tap of the last step + y;
+  (i) the picture only as a storage tap + y (what (h) is compared with, as (g) with (d));
+  (j) - (m) fp32 storage, 16 x 512x512, against the fp32 call without taps: 7 U16 taps + y, 7 fp32 storage taps + y,
+      the U16 picture + y, the fp32 storage picture + y.
 
 Device events around `--reps` calls after warm-up; every case is timed against (a) in the same process, A and B
 alternating for `--rounds` rounds; medians.  Each case is reported against its algorithmic bytes (12 B/px + 3 B/px per
-U8 tap or + 6 B/px per fp16 tap), as effective TB/s.  Also the CLI: `evaluate --step-by-step --batch 16` on 16 PNGs of
+U8 tap, + 6 B/px per fp16 or U16 tap, fp32 storage: 24 B/px + 12 B/px per fp32 tap), as effective TB/s.  Also the CLI: `evaluate --step-by-step --batch 16` on 16 PNGs of
 mixed sizes against `--step-by-step --stepwise`, wall time per image (one run each, after a warm-up run).
 usage: python tools/bench_fused_taps.py [--rounds 7] [--reps 20] [--out profiles/x.json]"""
 import argparse
@@ -66,10 +70,10 @@ def sequence(rng, n, steps, dev):
   return torch.from_numpy(ids).to(dev), torch.from_numpy(p).to(dev)
 
 
-def case(name, ms_a, ms_b, px, extra_bpp):
-  b = px * (12 + extra_bpp)
+def case(name, ms_a, ms_b, px, extra_bpp, base_bpp=12):
+  b = px * (base_bpp + extra_bpp)
   return dict(case=name, a_ms=ms_a, b_ms=ms_b, ratio=ms_b / ms_a, bytes=b, tbps=b / (ms_b * 1e-3) / 1e12,
-              a_tbps=px * 12 / (ms_a * 1e-3) / 1e12)
+              a_tbps=px * base_bpp / (ms_a * 1e-3) / 1e12)
 
 
 def cli_wall(paths, extra, out):
@@ -141,6 +145,34 @@ def main():
   res['cases'].append(case('f_24mp_5steps_4u8_y', a, b, 4000 * 6000, 12))
   print(json.dumps(res['cases'][-1]), flush=True)
   del big, yb, tb
+  # (g) - (i) U16 taps, fp16 storage: the tap planes are the storage taps' bytes
+  last = 1 << (steps - 1)
+  u16 = torch.empty((7, n, h, w, 3), dtype=torch.uint16, device=dev)
+  _cabi.chain_fused_fwd_taps(ids, p, x, y, m7, u16)
+  assert torch.equal(y.view(torch.int16), y0.view(torch.int16))
+  _cabi.chain_fused_fwd_taps(ids, p, x, y, last, st[:1])
+  assert torch.equal(evaluate.encode_u16(st[0]).view(torch.int16), evaluate.encode_u16(y0).view(torch.int16))
+  for name, fn, extra in (('g_7u16_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x, y, m7, u16), 42),
+                          ('h_u16_picture_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x, y, last, u16[:1]), 6),
+                          ('i_f16_picture_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x, y, last, st[:1]), 6)):
+    a, b = ab(fa, fn, args.rounds, args.reps)
+    res['cases'].append(case(name, a, b, px, extra))
+    print(json.dumps(res['cases'][-1]), flush=True)
+  # (j) - (m) the same with fp32 storage: the U16 planes go through the per-wave LDS stage
+  x32 = x.float()
+  y32 = torch.empty_like(x32)
+  st32 = torch.empty((7, n, h, w, 3), dtype=torch.float32, device=dev)
+
+  def fa32():
+    _cabi.chain_fused_fwd(ids, p, x32, y32)
+
+  for name, fn, extra in (('j_f32_7u16_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x32, y32, m7, u16), 42),
+                          ('k_f32_7f32_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x32, y32, m7, st32), 84),
+                          ('l_f32_u16_picture_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x32, y32, last, u16[:1]), 6),
+                          ('m_f32_f32_picture_y', lambda: _cabi.chain_fused_fwd_taps(ids, p, x32, y32, last, st32[:1]), 12)):
+    a, b = ab(fa32, fn, args.rounds, args.reps)
+    res['cases'].append(case(name, a, b, px, extra, 24))
+    print(json.dumps(res['cases'][-1]), flush=True)
   # the CLI on 16 mixed-size PNGs
   from PIL import Image
   with tempfile.TemporaryDirectory() as tmp:
