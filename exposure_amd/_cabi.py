@@ -95,6 +95,14 @@ SIGNATURES = {
     'expo_decode_workspace_bytes': (_sz, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
     'expo_decode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _fp, _i,
                                 ctypes.POINTER(_vp), _i, _vp, _sz, _vp]),
+    'expo_decode_tables_bytes': (_sz, [_i, _i, _i, _i]),
+    'expo_decode_tables': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _fp, _i, _vp, _sz,
+                                _i, _vp, _sz, _vp]),
+    'expo_bilinear_resize_ragged_codes': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i,
+                                               _vp, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
+    'expo_chain_fused_fwd_ragged_codes': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), _i, _i, _vp, _i, ctypes.POINTER(_vp),
+                                               ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
+                                               ctypes.POINTER(_vp), _vp]),
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -729,6 +737,166 @@ def decode_ragged(codes, table, normalize, outs, workspace=None):
       wsp, wsb = ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel() * workspace.element_size())
     _check(lib.expo_decode_ragged(_ptr_array(codes), hsa, wsa, n, c, bits, _ptr(table), int(normalize),
                                   _ptr_array(outs), _dtype_code(outs[0]), wsp, wsb, _stream()), 'expo_decode_ragged')
+
+
+_CODE_BITS = {torch.uint8: 8, torch.uint16: 16}
+
+
+def _codes_args(codes, dev):
+  """The lean per-image checks of the calls that read integer codes: N contiguous (H_i, W_i, C) device tensors, all
+  uint8 or all uint16, one C in {1, 3, 4} -> (bits, C, hs, ws)."""
+  ct = codes[0].dtype
+  bits = _CODE_BITS.get(ct)
+  if bits is None:
+    raise ExposureHipError('exposure_amd: codes must be uint8 or uint16 tensors, got %s' % ct)
+  if codes[0].dim() != 3:
+    raise ExposureHipError('exposure_amd: codes[0] must be (H, W, C), got %s' % (tuple(codes[0].shape),))
+  c, n = codes[0].shape[2], len(codes)
+  hs, ws = [0] * n, [0] * n
+  for i in range(n):
+    x = codes[i]
+    if not isinstance(x, torch.Tensor):
+      raise ExposureHipError('exposure_amd: codes[%d] must be a tensor' % i)
+    sx = x.shape
+    if len(sx) != 3 or sx[2] != c or x.dtype is not ct or x.get_device() != dev or not x.is_contiguous():
+      raise ExposureHipError('exposure_amd: codes[%d] %s must be a contiguous (H, W, %d) %s tensor on the device of '
+                             'the tables (HIP path only, no CPU fallback)' % (i, tuple(sx), c, ct))
+    hs[i], ws[i] = sx[0], sx[1]
+  return bits, c, hs, ws
+
+
+def _tables_arg(tables, stride, bits, n):
+  """tables / stride as ``decode_tables`` returns them: a contiguous float16 / float32 device tensor holding image i's
+  2^bits entries at i * stride (stride 0: one shared table)."""
+  if not isinstance(tables, torch.Tensor) or not tables.is_cuda or not tables.is_contiguous():
+    raise ExposureHipError('exposure_amd: tables must be a contiguous tensor on a ROCm device (decode_tables)')
+  stride = int(stride)
+  if stride != 0 and stride < (1 << bits):
+    raise ExposureHipError('exposure_amd: table stride %d is smaller than the %d entries of a table' % (stride, 1 << bits))
+  if tables.numel() < (n - 1) * stride + (1 << bits):
+    raise ExposureHipError('exposure_amd: tables holds %d entries, %d images at stride %d need %d' %
+                           (tables.numel(), n, stride, (n - 1) * stride + (1 << bits)))
+  return _dtype_code(tables), stride
+
+
+def decode_tables(codes, table, normalize, dtype, workspace=None):
+  """``expo_decode_tables``: the tables ``decode_ragged`` would gather from, without the gather -> (tables, stride).
+  codes, table, normalize, workspace as in ``decode_ragged``; dtype torch.float16 / float32 (the storage dtype).
+  normalize=1: tables (N, 2^bits), image i's normalised table in row i, stride 2^bits; normalize=0: ONE shared table
+  (1, 2^bits), stride 0.  ``tables[i * stride // 2^bits]`` gathered with image i's codes is what ``decode_ragged``
+  writes; ``bilinear_resize_ragged_codes`` and ``chain_fused_fwd_ragged_codes`` do that gather as they load."""
+  lib = load()
+  n = len(codes)
+  if n == 0:
+    raise ExposureHipError('exposure_amd: decode_tables needs at least one image')
+  dev = table.get_device()
+  bits, c, hs, ws = _codes_args(codes, dev)
+  if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape) != (1 << bits,):
+    raise ExposureHipError('exposure_amd: table must be a contiguous float32 device tensor of %d entries' % (1 << bits))
+  tables = torch.empty((n if normalize else 1, 1 << bits), dtype=dtype, device=table.device)
+  dtc = _dtype_code(tables)
+  hsa, wsa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws)
+  with torch.cuda.device(dev):
+    wsp, wsb = ctypes.c_void_p(0), ctypes.c_size_t(0)
+    if normalize:
+      need = int(lib.expo_decode_workspace_bytes(n, hsa, wsa, c, bits))
+      if workspace is None:
+        workspace = reserve_workspace(table.device, need)
+        _order_shared_workspace(table.device)
+      if not workspace.is_cuda or workspace.device != table.device or workspace.numel() * workspace.element_size() < need:
+        raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' %
+                               (need, table.device))
+      wsp, wsb = ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel() * workspace.element_size())
+    rc = lib.expo_decode_tables(_ptr_array(codes), hsa, wsa, n, c, bits, _ptr(table), int(normalize), _ptr(tables),
+                                tables.numel() * tables.element_size(), dtc, wsp, wsb, _stream())
+    if rc < 0:
+      _check(rc, 'expo_decode_tables')
+  return tables, rc
+
+
+def bilinear_resize_ragged_codes(codes, tables, stride, windows, S, out):
+  """``expo_bilinear_resize_ragged_codes``: ``bilinear_resize_ragged`` of the images ``decode_ragged`` would make of
+  ``codes``, read from the codes and their tables (``decode_tables``): the float images need not exist.  windows, S,
+  out as in ``bilinear_resize_ragged``."""
+  import numpy as np
+  lib = load()
+  rec = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 4))
+  q, n = rec.shape[0], len(codes)
+  _img(out, 'out')
+  if tuple(out.shape) != (q, S, S, 3):
+    raise ExposureHipError('exposure_amd: out must be (%d, %d, %d, 3), got %s' % (q, S, S, tuple(out.shape)))
+  if q == 0:
+    return out
+  if n == 0:
+    raise ExposureHipError('exposure_amd: windows need images')
+  dev = out.get_device()
+  bits, c, hs, ws = _codes_args(codes, dev)
+  tdt, stride = _tables_arg(tables, stride, bits, n)
+  if tables.get_device() != dev:
+    raise ExposureHipError('exposure_amd: tables must be on the device of out')
+  with torch.cuda.device(out.device):
+    _check(lib.expo_bilinear_resize_ragged_codes(_ptr_array(codes), (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, c,
+                                                 bits, _ptr(tables), stride, tdt,
+                                                 rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), q, int(S), _ptr(out),
+                                                 _dtype_code(out), _stream()), 'expo_bilinear_resize_ragged_codes')
+  return out
+
+
+def chain_fused_fwd_ragged_codes(filter_ids, params, codes, tables, stride, ys, tap_mask=0, taps=None):
+  """``chain_fused_fwd_ragged_taps`` with the input of image i given as its integer codes plus its table
+  (``expo_chain_fused_fwd_ragged_codes``): codes as in ``decode_ragged``, tables / stride from ``decode_tables`` in the
+  storage dtype.  ys: N contiguous device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3) of the tables' dtype, or None (taps
+  only); tap_mask may be 0 (taps None); taps as in ``chain_fused_fwd_ragged_taps``."""
+  lib = load()
+  n = len(codes)
+  if ys is not None and len(ys) != n:
+    raise ExposureHipError('exposure_amd: codes and ys must have the same length')
+  if taps is not None and len(taps) != n:
+    raise ExposureHipError('exposure_amd: codes and taps must have the same length')
+  if filter_ids.dim() != 2 or filter_ids.shape[0] != n or not filter_ids.is_cuda or filter_ids.dtype != torch.int32 or \
+      not filter_ids.is_contiguous():
+    raise ExposureHipError('exposure_amd: filter_ids must be a contiguous int32 device tensor of shape (N, steps)')
+  steps = filter_ids.shape[1]
+  _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
+  t = _tap_count(tap_mask, steps)
+  if ys is None and not t:
+    raise ExposureHipError('exposure_amd: nothing to write (ys None and tap_mask 0)')
+  if t and taps is None:
+    raise ExposureHipError('exposure_amd: tap_mask 0x%x needs taps' % tap_mask)
+  if n == 0:
+    return
+  dev = filter_ids.get_device()
+  if params.get_device() != dev:
+    raise ExposureHipError('exposure_amd: filter_ids and params must be on the images\' device')
+  bits, c, hs, ws = _codes_args(codes, dev)
+  dtc, stride = _tables_arg(tables, stride, bits, n)
+  dt = tables.dtype
+  if tables.get_device() != dev:
+    raise ExposureHipError('exposure_amd: tables must be on the device of filter_ids')
+  fmt, tdt = EXPO_TAP_STORAGE, None
+  if taps is not None:
+    fmt, tdt = _tap_format(taps[0], dt), taps[0].dtype
+  for i in range(n):
+    h, w = hs[i], ws[i]
+    if ys is not None:
+      y = ys[i]
+      if not isinstance(y, torch.Tensor) or tuple(y.shape[-3:]) != (h, w, 3) or \
+          not (y.dim() == 3 or (y.dim() == 4 and y.shape[0] == 1)) or y.dtype is not dt or y.get_device() != dev or \
+          not y.is_contiguous():
+        raise ExposureHipError('exposure_amd: ys[%d] must be a contiguous (%d, %d, 3) or (1, %d, %d, 3) device tensor '
+                               'of the tables\' dtype' % (i, h, w, h, w))
+    if taps is not None:
+      tp = taps[i]
+      if not isinstance(tp, torch.Tensor) or tp.shape != (t, h, w, 3) or tp.dtype is not tdt or \
+          tp.get_device() != dev or not tp.is_contiguous():
+        raise ExposureHipError('exposure_amd: taps[%d] must be a contiguous device tensor (%d, %d, %d, 3) of the '
+                               'dtype of taps[0]' % (i, t, h, w))
+  with torch.cuda.device(dev):
+    _check(lib.expo_chain_fused_fwd_ragged_codes(_ptr(filter_ids), _ptr(params), steps, _ptr_array(codes), c, bits,
+                                                 _ptr(tables), stride, None if ys is None else _ptr_array(ys),
+                                                 (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, dtc, tap_mask, fmt,
+                                                 None if not t else _ptr_array(taps), _stream()),
+           'expo_chain_fused_fwd_ragged_codes')
 
 
 def area_resize_ragged(xs, windows, S, out):

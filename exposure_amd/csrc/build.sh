@@ -1,10 +1,12 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Twelve translation units; extra arguments go to every compile step.
+# Fourteen translation units; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
 #   chain_fused.hip      the VALU-bound fused inference kernel (-fno-slp-vectorize -fno-honor-nans, see the file)
+#   chain_fused_codes.hip  the fused inference pass reading the files' integer codes (exactly chain_fused.hip's flags:
+#                        it includes that file for the step loop and the stores and must reproduce its outputs bit for bit)
 #   chain_fused_bwd.hip  the one-pass backward of a fixed sequence (-fno-slp-vectorize: the packed-fp32 pairs cost it
 #                        ~100 VGPRs)
 #   nn_ops.hip           the convnets' activation and glue
@@ -16,6 +18,8 @@
 #   datasets.hip         the training sets' INTER_AREA master pack and its per-epoch re-cut (default flags)
 #   proxy.hip            the agent's bilinear 64x64 proxies of a ragged batch (-ffp-contract=off: every operation of
 #                        its definition is rounded on its own, so the host restatement matches bit for bit)
+#   proxy_codes.hip      the same proxies read from the files' integer codes (exactly proxy.hip's flags: it includes that file
+#                        for the arithmetic)
 #   metric.hip           the evaluation metric's patch statistics and their histograms (default flags)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -51,6 +55,10 @@ p11=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/metric.hip" -o "$TMP/metric.o" &
 p12=$!
 # (a bare `wait` returns 0 whatever the jobs did: wait for each PID so a failed compile stops the script here)
+"$HIPCC" "${FLAGS[@]}" -fno-slp-vectorize -fno-honor-nans "$@" -c "$HERE/chain_fused_codes.hip" -o "$TMP/chain_fused_codes.o" &
+p13=$!
+"$HIPCC" "${FLAGS[@]}" -ffp-contract=off "$@" -c "$HERE/proxy_codes.hip" -o "$TMP/proxy_codes.o" &
+p14=$!
 wait $p1
 wait $p2
 wait $p3
@@ -63,5 +71,7 @@ wait $p9
 wait $p10
 wait $p11
 wait $p12
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" -o "$OUT"
+wait $p13
+wait $p14
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -847,6 +847,9 @@ static int check_taps(int steps, uint64_t tap_mask, int tap_format) {
 
 }  // namespace expo
 
+// (chain_fused_codes.hip includes this file for the templates above and defines this: the exports below, and with them
+// every instantiation of the kernels above, belong to this unit alone)
+#ifndef EXPO_CHAIN_FUSED_TEMPLATES_ONLY
 using namespace expo;
 
 extern "C" {
@@ -966,3 +969,4 @@ int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* p
 }
 
 }  // extern "C"
+#endif  // EXPO_CHAIN_FUSED_TEMPLATES_ONLY

@@ -1,0 +1,294 @@
+// chain_fused_codes.hip -- the fused ragged inference pass straight from the integer codes of the image files
+// (expo_chain_fused_fwd_ragged_codes).  expo_chain_fused_fwd_ragged_taps with another loader: the
+// input of image i is its codes (8 or 16 bits, 1, 3 or 4 channels, as the file holds them) plus its table in the
+// storage dtype T (expo_decode_tables), and a pixel value enters the step loop as float(T table[code]) -- the very value
+// the decoded tensor would have held, so the outputs are bit-identical to decode + pass and the float input never exists.
+//
+// A unit of its own, compiled with exactly chain_fused.hip's flags (csrc/build.sh): it includes that file for
+// chain_fused_run, TapSink and the stores, which it uses untouched, and instantiates none of its kernels
+// (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), so the kernels of chain_fused.hip keep their code and registers and the two units
+// compile side by side.  The only device code of its own is the loader below.
+//   vector path       a lane's group keeps pixel_io.h's pixel positions: row r of a wave's chunk is the 12-byte vector
+//                     of PPV pixels (fp16 2, fp32 1) at pixel gw * PPL + r * 64 * PPV + lane * PPV; its PPV * C codes
+//                     come in with the widest buffer load their size allows, as decode_kernel's.  Rows past the end of
+//                     the image read code 0 and their stores are dropped by the bounds checks.
+//   element-wise path per image, block-uniform: codes not 4-byte aligned, hw % PPV != 0, or y / a vector-stored tap
+//                     plane misaligned (the rule of chain_fused.hip with the codes' base added).
+//   tables            an 8-bit table is staged in LDS once per block (a block belongs to one image; 512 B / 1 KiB); a
+//                     16-bit table (128 / 256 KiB per image) is read through the caches.
+#define EXPO_CHAIN_FUSED_TEMPLATES_ONLY
+#include "chain_fused.hip"
+
+namespace expo {
+
+namespace {
+
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+// up to 64 images by value in the kernel arguments (2 KB): codes, output (NULL: none), tap buffer, pixel count, first
+// block of each image (first[n] = the grid's size) and a bit per image for the vector path
+template <typename T>
+struct CodesTable {
+  const void* codes[kRaggedMaxImages];
+  T* y[kRaggedMaxImages];
+  char* taps[kRaggedMaxImages];
+  int hw[kRaggedMaxImages];
+  int first[kRaggedMaxImages + 1];
+  int n;
+  uint64_t vec;
+};
+// kernel arguments: ids, params, steps, tap_mask, tables, table_stride, the table
+static_assert(sizeof(CodesTable<half_t>) + 48 <= 4096, "the codes table must fit the 4 KB kernarg block");
+
+// the NB = PPV * C * sizeof(CT) code bytes of one lane-row at byte offset off (a multiple of NB; the base is 4-byte
+// aligned), with the widest load their size allows
+template <typename CT, int NB, int AUX>
+__device__ __forceinline__ void load_code_row(__amdgpu_buffer_rsrc_t rin, int off, CT* c) {
+  if constexpr (NB == 16) {
+    const u32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, AUX);
+    __builtin_memcpy(c, &q, NB);
+  } else if constexpr (NB == 12) {
+    const u32x3_t q = __builtin_amdgcn_raw_buffer_load_b96(rin, off, 0, AUX);
+    __builtin_memcpy(c, &q, NB);
+  } else if constexpr (NB == 8) {
+    const u32x2_t q = __builtin_amdgcn_raw_buffer_load_b64(rin, off, 0, AUX);
+    __builtin_memcpy(c, &q, NB);
+  } else if constexpr (NB == 4) {
+    const uint32_t q = __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, AUX);
+    __builtin_memcpy(c, &q, NB);
+  } else if constexpr (NB % 2 == 0) {  // 2 or 6 bytes: 2-byte aligned
+    uint16_t q[NB / 2];
+#pragma unroll
+    for (int k = 0; k < NB / 2; ++k) q[k] = __builtin_amdgcn_raw_buffer_load_b16(rin, off + 2 * k, 0, AUX);
+    __builtin_memcpy(c, q, NB);
+  } else {  // 1 or 3 bytes
+    uint8_t q[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) q[k] = __builtin_amdgcn_raw_buffer_load_b8(rin, off + k, 0, AUX);
+    __builtin_memcpy(c, q, NB);
+  }
+}
+
+// chain_fused_image_taps with the codes loader; Sink = NoSink: no taps.  look(code) is the table gather.  yi may be
+// NULL with taps.  One chunk per wave and trip, the next trip `stride` groups on (the ragged grid covers an image's
+// groups in one trip).
+template <typename CT, int C, typename T, bool VEC, class IO, class Sink, class Look>
+__device__ __forceinline__ void chain_fused_codes_image(const int32_t* idn, const float* prn, int steps, const CT* codes,
+                                                        T* yi, int hw, int groups, int first_gw, int stride,
+                                                        float2_lut* tab, const Sink& sink, const Look& look) {
+  constexpr int PPL = PixTraits<T>::PPL, PPV = VecTraits<T>::PPV;
+  constexpr bool kTaps = !std::is_same<Sink, NoSink>::value;
+  const int lane = threadIdx.x & 63;
+  const int plane = lane % EXPO_MAX_PARAMS;
+  auto run = [&](float* v, int gw) {
+    if constexpr (kTaps)
+      chain_fused_run<T>(idn, prn, steps, tab, plane, v, [&](int k, const float* o) { sink(k, gw, lane, o); });
+    else
+      chain_fused_run<T>(idn, prn, steps, tab, plane, v);
+  };
+  if constexpr (VEC) {
+#if EXPO_FP16_OVFL
+    // the fp16 stores (y and storage taps) saturate as in stream_groups
+    if constexpr (sizeof(T) == 2) __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);
+#endif
+    constexpr int NB = PPV * C * int(sizeof(CT));  // code bytes per lane-row
+    const __amdgpu_buffer_rsrc_t rin =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<CT*>(codes), 0, hw * C * int(sizeof(CT)), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t ry = make_image_rsrc(yi, hw);
+    for (int gw = first_gw; gw * PPL < hw; gw += stride) {  // wave-uniform
+      CT c[4][PPV * C];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        load_code_row<CT, NB, IO::kLoadX>(rin, (gw * PPL + r * 64 * PPV + lane * PPV) * C * int(sizeof(CT)), c[r]);
+      float v[PPL * 3];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int p = 0; p < PPV; ++p) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) v[(r * PPV + p) * 3 + ch] = float(look(c[r][p * C + (C == 1 ? 0 : ch)]));
+        }
+      }
+      run(v, gw);
+      if (yi) store_raw<IO::kStore>(ry, chunk_byte_offset<T>(gw, lane), pack<T>(v));
+    }
+  } else {
+    for (int g0 = first_gw; g0 < groups; g0 += stride) {  // wave-uniform trip count, as chain_fused_image
+      const int g = g0 + lane;
+      float v[PPL * 3];
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) {
+        const int px = g * PPL + k;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          v[k * 3 + ch] = px < hw ? float(look(codes[size_t(px) * C + (C == 1 ? 0 : ch)])) : 0.0f;
+      }
+      run(v, g0);
+      if (yi) store_slow<T>(yi, g, hw, v);
+    }
+  }
+}
+
+// FMT: an EXPO_TAP_* format, or kTapNone (tap_mask == 0).  Both paths in every kernel: the choice is block-uniform.
+template <typename CT, int C, typename T, class IO, int FMT>
+__global__ __launch_bounds__(kThreads) void chain_fused_fwd_ragged_codes_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ params, int steps, uint64_t tap_mask,
+    const T* __restrict__ tables, int table_stride, const CodesTable<T> tab) {
+  constexpr bool LDS = sizeof(CT) == 1;
+  static_assert(!LDS || kThreads == 256, "one thread per entry of an 8-bit table");
+  __shared__ float2_lut curve_tab[kWaves][32];
+  __shared__ __attribute__((aligned(4))) uint8_t tap_stage[kWaves][TapStage<T, FMT>::kBytes];
+  __shared__ T lut[LDS ? 256 : 1];
+  const int b = blockIdx.x;
+  int lo = 0, hi = tab.n - 1;  // the last image whose first block is <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab.first[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int i = __builtin_amdgcn_readfirstlane(lo);
+  constexpr int PPL = PixTraits<T>::PPL;
+  const T* ttab = tables + size_t(i) * size_t(table_stride);
+  if constexpr (LDS) {  // before any wave leaves: every thread stages one entry
+    lut[threadIdx.x] = ttab[threadIdx.x];
+    __syncthreads();
+  }
+  auto look = [&](uint32_t k) -> T {
+    if constexpr (LDS) return lut[k];
+    else return ttab[k];
+  };
+  const int hw = tab.hw[i];
+  const int groups = (hw + PPL - 1) / PPL;
+  const int first_gw = (b - tab.first[i]) * kThreads + (threadIdx.x & ~63);
+  const int stride = (tab.first[i + 1] - tab.first[i]) * kThreads;
+  const int32_t* idn = ids + size_t(i) * steps;
+  const float* prn = params + size_t(i) * steps * EXPO_MAX_PARAMS;
+  float2_lut* const curve = curve_tab[threadIdx.x >> 6];
+  const CT* codes = static_cast<const CT*>(tab.codes[i]);
+  auto image = [&](auto vec) {
+    constexpr bool VEC = decltype(vec)::value;
+    if constexpr (FMT == kTapNone) {
+      chain_fused_codes_image<CT, C, T, VEC, IO>(idn, prn, steps, codes, tab.y[i], hw, groups, first_gw, stride, curve,
+                                                 NoSink(), look);
+    } else {
+      using Sink = TapSink<T, VEC, IO, FMT>;
+      const Sink sink{tab.taps[i], size_t(hw) * 3 * Sink::ES, tap_mask, hw, tap_stage[threadIdx.x >> 6]};
+      chain_fused_codes_image<CT, C, T, VEC, IO>(idn, prn, steps, codes, tab.y[i], hw, groups, first_gw, stride, curve,
+                                                 sink, look);
+    }
+  };
+  if ((tab.vec >> i) & 1) image(std::true_type());
+  else image(std::false_type());
+}
+
+// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output
+template <typename CT, int C, typename T, int FMT>
+int chain_fused_codes_t(const int32_t* ids, const float* params, int steps, const void* const* codes, const void* tables,
+                        int table_stride, void* const* ys, const int* hs, const int* ws, int n, uint64_t tap_mask,
+                        void* const* taps, hipStream_t s) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  long bytes = 0;  // cache policy from the bytes of the whole call, as the pass from tensors
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kRaggedMaxImages) {
+    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
+    CodesTable<T> tab = {};
+    tab.n = m;
+    long blocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      tab.codes[j] = codes[i];
+      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+      tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
+      tab.hw[j] = hw;
+      tab.first[j] = int(blocks);
+      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
+      const uintptr_t a = reinterpret_cast<uintptr_t>(codes[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
+                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
+      if (hw % VecTraits<T>::PPV == 0 && (a & 3) == 0) tab.vec |= uint64_t(1) << j;
+    }
+    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    tab.first[m] = int(blocks);
+    const int32_t* idb = ids + size_t(base) * steps;
+    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
+    const T* tb = static_cast<const T*>(tables) + size_t(base) * size_t(table_stride);
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
+    if (stream)
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoStream, FMT>), grid, block, 0, s, idb, prb, steps,
+                         tap_mask, tb, table_stride, tab);
+    else
+      hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoCached, FMT>), grid, block, 0, s, idb, prb, steps,
+                         tap_mask, tb, table_stride, tab);
+    HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged_codes launch");
+  }
+  return EXPO_OK;
+}
+
+template <typename CT, int C, typename T>
+int chain_fused_codes_fmt(uint64_t tap_mask, int tap_format, const int32_t* ids, const float* params, int steps,
+                          const void* const* codes, const void* tables, int table_stride, void* const* ys, const int* hs,
+                          const int* ws, int n, void* const* taps, hipStream_t s) {
+#define EXPO_CODES(FMT) \
+  chain_fused_codes_t<CT, C, T, FMT>(ids, params, steps, codes, tables, table_stride, ys, hs, ws, n, tap_mask, taps, s)
+  if (!tap_mask) return EXPO_CODES(kTapNone);
+  if (tap_format == EXPO_TAP_U8) return EXPO_CODES(EXPO_TAP_U8);
+  if (tap_format == EXPO_TAP_U16) return EXPO_CODES(EXPO_TAP_U16);
+  return EXPO_CODES(EXPO_TAP_STORAGE);
+#undef EXPO_CODES
+}
+
+template <typename CT, int C, typename... A>
+int chain_fused_codes_dtype(int dtype, A... a) {
+  return dtype == EXPO_F16 ? chain_fused_codes_fmt<CT, C, half_t>(a...) : chain_fused_codes_fmt<CT, C, float>(a...);
+}
+
+template <typename CT, typename... A>
+int chain_fused_codes_channels(int channels, int dtype, A... a) {
+  if (channels == 1) return chain_fused_codes_dtype<CT, 1>(dtype, a...);
+  if (channels == 3) return chain_fused_codes_dtype<CT, 3>(dtype, a...);
+  return chain_fused_codes_dtype<CT, 4>(dtype, a...);
+}
+
+}  // namespace
+
+}  // namespace expo
+
+using namespace expo;
+
+extern "C" {
+
+int expo_chain_fused_fwd_ragged_codes(const int32_t* filter_ids, const float* params, int steps,
+                                      const void* const* codes, int channels, int code_bits, const void* tables,
+                                      int table_stride, void* const* ys, const int* hs, const int* ws, int n, int dtype,
+                                      uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+  if (channels != 1 && channels != 3 && channels != 4) return fail(EXPO_E_BADARG, "channels must be 1, 3 or 4");
+  if (code_bits != 8 && code_bits != 16) return fail(EXPO_E_BADARG, "code_bits must be 8 or 16");
+  if (table_stride != 0 && table_stride < (1 << code_bits))
+    return fail(EXPO_E_BADARG, "table_stride must be 0 (one shared table) or at least 2^code_bits entries");
+  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
+  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
+  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
+  if (n == 0) return EXPO_OK;
+  if (!codes || !tables || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
+    return fail(EXPO_E_BADARG, "null pointer");
+  if ((reinterpret_cast<uintptr_t>(tables) & 3) != 0) return fail(EXPO_E_BADARG, "tables must be 4-byte aligned");
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
+    if (long(hs[i]) * ws[i] * channels * (code_bits / 8) > (1L << 31) - 8192)
+      return fail(EXPO_E_BADARG, "the codes of one image must be smaller than 2 GiB");
+    if (!codes[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
+    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (code_bits == 8)
+    return chain_fused_codes_channels<uint8_t>(channels, dtype, tap_mask, tap_format, filter_ids, params, steps, codes,
+                                               tables, table_stride, ys, hs, ws, n, taps, s);
+  return chain_fused_codes_channels<uint16_t>(channels, dtype, tap_mask, tap_format, filter_ids, params, steps, codes,
+                                              tables, table_stride, ys, hs, ws, n, taps, s);
+}
+
+}  // extern "C"

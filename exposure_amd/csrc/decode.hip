@@ -11,6 +11,10 @@
 //                         default, correctly rounded division: no fast-math, no -fno-honor-nans)
 //   decode_kernel         gather only; 8-bit tables are staged in LDS, 16-bit ones are read through L2
 // Without normalisation it is the decode launch alone, casting the caller's table on the fly.
+// expo_decode_tables / expo_decode_tables_bytes stop after the tables: decode_max_kernel and
+// decode_finish_kernel as above, the finish writing into the caller's buffer, or decode_cast_kernel for the one shared
+// table T(table[k]) of a call without normalisation.  Their consumers gather at load time (proxy.hip,
+// chain_fused_codes.hip).
 #include <limits.h>
 
 #include "host_common.h"
@@ -120,7 +124,10 @@ __global__ __launch_bounds__(kThreads) void decode_max_kernel(const DecodeTable 
 
 // grid (slices, images): every block finds image j's largest code from its records (first[] of the max pass), then
 // writes its slice of the normalised table T(table[k] / (2 table[m])); all-zero codes give 0 / 0 = NaN, as numpy
-template <typename T, int BITS>
+// NAN_TABLE (expo_decode_tables): a table whose divisor is 0 is NaN in EVERY entry, not only in those the image's codes
+// read (entry k > 0 of an all-zero image would be table[k] / 0 = inf; no code of the image reads it, so a gather gives
+// the same either way).  The instantiation of expo_decode_ragged is the kernel as it was.
+template <typename T, int BITS, bool NAN_TABLE = false>
 __global__ __launch_bounds__(kThreads) void decode_finish_kernel(const DecodeTable tab, const uint32_t* __restrict__ records,
                                                                  const float* __restrict__ table, T* __restrict__ tables) {
   constexpr int entries = 1 << BITS;
@@ -128,11 +135,20 @@ __global__ __launch_bounds__(kThreads) void decode_finish_kernel(const DecodeTab
   uint32_t m = 0;
   for (int r = tab.first[j] + threadIdx.x; r < tab.first[j + 1]; r += kThreads) m = max(m, records[r]);
   m = block_max(m);
-  const float d = 2.0f * table[m];
+  float d = 2.0f * table[m];
+  if constexpr (NAN_TABLE) d = d == 0.0f ? __builtin_nanf("") : d;
   T* tj = tables + size_t(j) * entries;
   const int e0 = blockIdx.x * kFinishEntries;
   const int e1 = min(entries, e0 + kFinishEntries);
   for (int e = e0 + threadIdx.x; e < e1; e += kThreads) tj[e] = T(table[e] / d);
+}
+
+// the shared table of a call without normalisation, in the storage dtype
+template <typename T>
+__global__ __launch_bounds__(kThreads) void decode_cast_kernel(const float* __restrict__ table, T* __restrict__ tables,
+                                                               int entries) {
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  if (e < entries) tables[e] = T(table[e]);
 }
 
 // The gather.  Vector path (codes and output 4-byte aligned, whole 12-byte output vectors): a lane-row is the
@@ -306,6 +322,61 @@ int decode_ragged_t(const void* const* codes, const int* hs, const int* ws, int 
   return EXPO_OK;
 }
 
+// arguments validated by the caller; normalize: image i's table at tables + i * 2^BITS, the records of a launch in the
+// workspace (launches reuse it in stream order)
+template <typename CT, int C, typename T>
+int decode_tables_t(const void* const* codes, const int* hs, const int* ws, int n, const float* table, void* tables,
+                    void* workspace, hipStream_t s) {
+  constexpr int BITS = 8 * int(sizeof(CT));
+  long bytes = 0;
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * C * long(sizeof(CT));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kDecodeMaxImages) {
+    const int m = n - base < kDecodeMaxImages ? n - base : kDecodeMaxImages;
+    DecodeTable mt = {};
+    mt.n = m;
+    long mblocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      mt.codes[j] = codes[i];
+      mt.hw[j] = hw;
+      mt.first[j] = int(mblocks);
+      mblocks += max_blocks(long(hw) * C * long(sizeof(CT)));
+      if ((reinterpret_cast<uintptr_t>(codes[i]) & 3) == 0) mt.vec |= uint64_t(1) << j;
+    }
+    if (mblocks > INT_MAX) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    mt.first[m] = int(mblocks);
+    const dim3 block(kThreads);
+    uint32_t* rec = static_cast<uint32_t*>(workspace);
+    T* ttab = static_cast<T*>(tables) + (size_t(base) << BITS);
+    if (stream)
+      hipLaunchKernelGGL((decode_max_kernel<CT, C, IoStream>), dim3(unsigned(mblocks)), block, 0, s, mt, rec);
+    else
+      hipLaunchKernelGGL((decode_max_kernel<CT, C, IoCached>), dim3(unsigned(mblocks)), block, 0, s, mt, rec);
+    HIP_TRY(hipGetLastError(), "decode_max launch");
+    const int slices = (1 << BITS) > kFinishEntries ? (1 << BITS) / kFinishEntries : 1;
+    hipLaunchKernelGGL((decode_finish_kernel<T, BITS, true>), dim3(slices, m), block, 0, s, mt, rec, table, ttab);
+    HIP_TRY(hipGetLastError(), "decode_finish launch");
+  }
+  return EXPO_OK;
+}
+
+template <typename CT, typename T>
+int decode_tables_channels(int channels, const void* const* codes, const int* hs, const int* ws, int n,
+                           const float* table, void* tables, void* workspace, hipStream_t s) {
+  if (channels == 1) return decode_tables_t<CT, 1, T>(codes, hs, ws, n, table, tables, workspace, s);
+  if (channels == 3) return decode_tables_t<CT, 3, T>(codes, hs, ws, n, table, tables, workspace, s);
+  return decode_tables_t<CT, 4, T>(codes, hs, ws, n, table, tables, workspace, s);
+}
+
+template <typename T>
+int decode_cast_t(const float* table, void* tables, int entries, hipStream_t s) {
+  hipLaunchKernelGGL((decode_cast_kernel<T>), dim3(unsigned((entries + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                     table, static_cast<T*>(tables), entries);
+  HIP_TRY(hipGetLastError(), "decode_cast launch");
+  return EXPO_OK;
+}
+
 template <typename CT, typename T>
 int decode_channels(int channels, const void* const* codes, const int* hs, const int* ws, int n, const float* table,
                     int normalize, void* const* outs, void* workspace, hipStream_t s) {
@@ -365,6 +436,54 @@ int expo_decode_ragged(const void* const* codes, const int* hs, const int* ws, i
                              : decode_channels<uint8_t, float>(channels, codes, hs, ws, n, table, normalize, outs, workspace, s);
   return dtype == EXPO_F16 ? decode_channels<uint16_t, half_t>(channels, codes, hs, ws, n, table, normalize, outs, workspace, s)
                            : decode_channels<uint16_t, float>(channels, codes, hs, ws, n, table, normalize, outs, workspace, s);
+}
+
+size_t expo_decode_tables_bytes(int n, int code_bits, int normalize, int dtype) {
+  if (n < 1 || (code_bits != 8 && code_bits != 16) || (normalize != 0 && normalize != 1) ||
+      (dtype != EXPO_F16 && dtype != EXPO_F32))
+    return 0;
+  return (size_t(normalize ? n : 1) << code_bits) * (dtype == EXPO_F16 ? 2 : 4);
+}
+
+int expo_decode_tables(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
+                       const float* table, int normalize, void* tables, size_t tables_bytes, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (channels != 1 && channels != 3 && channels != 4) return fail(EXPO_E_BADARG, "channels must be 1, 3 or 4");
+  if (code_bits != 8 && code_bits != 16) return fail(EXPO_E_BADARG, "code_bits must be 8 or 16");
+  if (normalize != 0 && normalize != 1) return fail(EXPO_E_BADARG, "normalize must be 0 or 1");
+  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+  if (n == 0) return 0;
+  if (!table || !tables || (normalize && (!codes || !hs || !ws))) return fail(EXPO_E_BADARG, "null pointer");
+  if ((reinterpret_cast<uintptr_t>(tables) & 3) != 0) return fail(EXPO_E_BADARG, "tables must be 4-byte aligned");
+  if (tables_bytes < expo_decode_tables_bytes(n, code_bits, normalize, dtype))
+    return fail(EXPO_E_BADARG, "tables buffer too small (expo_decode_tables_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!normalize) {
+    const int rc = dtype == EXPO_F16 ? decode_cast_t<half_t>(table, tables, 1 << code_bits, s)
+                                     : decode_cast_t<float>(table, tables, 1 << code_bits, s);
+    return rc;  // EXPO_OK = 0: one shared table
+  }
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
+    if (long(hs[i]) * ws[i] * channels * (code_bits / 8) > (1L << 31) - 8192)
+      return fail(EXPO_E_BADARG, "the codes of one image must be smaller than 2 GiB");
+    if (!codes[i]) return fail(EXPO_E_BADARG, "null image pointer");
+  }
+  const long need = workspace_need(n, hs, ws, channels, code_bits);
+  if (need < 0) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
+    return fail(EXPO_E_BADARG, "normalize needs a 4-byte aligned workspace");
+  if (workspace_bytes < size_t(need)) return fail(EXPO_E_BADARG, "workspace too small (expo_decode_workspace_bytes)");
+  int rc;
+  if (code_bits == 8)
+    rc = dtype == EXPO_F16 ? decode_tables_channels<uint8_t, half_t>(channels, codes, hs, ws, n, table, tables, workspace, s)
+                           : decode_tables_channels<uint8_t, float>(channels, codes, hs, ws, n, table, tables, workspace, s);
+  else
+    rc = dtype == EXPO_F16 ? decode_tables_channels<uint16_t, half_t>(channels, codes, hs, ws, n, table, tables, workspace, s)
+                           : decode_tables_channels<uint16_t, float>(channels, codes, hs, ws, n, table, tables, workspace, s);
+  return rc != EXPO_OK ? rc : 1 << code_bits;
 }
 
 }  // extern "C"

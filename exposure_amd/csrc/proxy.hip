@@ -108,6 +108,9 @@ int bilinear_resize_t(const void* const* xs, const int* ws, const int32_t* windo
 
 }  // namespace expo
 
+// (proxy_codes.hip includes this file for the arithmetic above and defines this: the export below, and with it the
+// kernels above, belong to this unit alone)
+#ifndef EXPO_PROXY_TEMPLATES_ONLY
 using namespace expo;
 
 extern "C" {
@@ -143,3 +146,4 @@ int expo_bilinear_resize_ragged(const void* const* xs, const int* hs, const int*
 }
 
 }  // extern "C"
+#endif  // EXPO_PROXY_TEMPLATES_ONLY

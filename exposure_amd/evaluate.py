@@ -502,6 +502,101 @@ def decode_images(raws, dtype, device):
   return outs
 
 
+def upload_codes(codes, device):
+  """The codes of one ``load_raw`` result on the device, as they are (PIL's arrays are read-only: they are only read)."""
+  with warnings.catch_warnings():
+    warnings.simplefilter('ignore', UserWarning)
+    return torch.from_numpy(np.ascontiguousarray(codes)).to(device)
+
+
+@torch.no_grad()
+def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_masks=None, return_trace=False,
+                      intermediates=None, picture=False, outputs=True):
+  """``retouch_batch(agent, decode_images(raws, dtype, device), proxy='device', ...)`` without the decoded tensors
+  (DESIGN.md §3.23): ``raws`` are ``load_raw`` results, and the integer codes are what the device reads.  Per
+  (kind, channels) group of the batch ``_cabi.decode_tables`` writes the tables ``decode_ragged`` would gather from;
+  then the 64x64 proxies of the whole batch, stacked in argument order, come from one
+  ``_cabi.bilinear_resize_ragged_codes`` call per group, the agent runs once, and one
+  ``_cabi.chain_fused_fwd_ragged_codes`` launch per group applies that group's rows of ids and params to the codes.
+  Every returned value is bit for bit the one of the call above.
+
+  ``outputs=False`` allocates no float output: the first entry is a list of ``None`` (it needs ``picture`` or
+  ``intermediates``: something must be written).  ``cfg.masking``, or a ``cfg.curve_steps`` that needs the generic
+  kernels, raises ``ValueError``: there is no pass from codes for them and no silent fallback."""
+  from . import _cabi
+  cfg = agent.cfg
+  if intermediates not in INTERMEDIATES:
+    raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
+  kind = _picture_kind(picture, intermediates)
+  if cfg.masking:
+    raise ValueError('retouch_batch_raw: cfg.masking has no pass from codes (decode_images + retouch_batch)')
+  if any(f.uses_generic_kernels() for f in agent.filters):
+    raise ValueError('retouch_batch_raw: cfg.curve_steps = %s needs the generic kernels, which have no pass from codes '
+                     '(decode_images + retouch_batch)' % (cfg.curve_steps,))
+  raws = list(raws)
+  n = len(raws)
+  if n == 0:
+    raise ValueError('retouch_batch_raw: no images')
+  if not outputs and not kind and not intermediates:
+    raise ValueError('retouch_batch_raw: outputs=False needs picture or intermediates (nothing would be written)')
+  dev = torch.device(device)
+  steps = steps or cfg.test_steps
+  if z is None:
+    z = torch.rand((n, cfg.z_dim), device=dev)
+  groups = {}
+  for i, (codes, k) in enumerate(raws):
+    groups.setdefault((k, codes.shape[2]), []).append(i)
+  size = cfg.source_img_size
+  low = torch.empty((n, size, size, 3), dtype=dtype, device=dev)
+  staged = []  # per group: the images' indices, their codes on the device, the tables and their stride
+  for (k, _c), idx in groups.items():
+    cs = [upload_codes(raws[i][0], dev) for i in idx]
+    tables, stride = _cabi.decode_tables(cs, decode_table(k, dev), DECODE_NORMALIZE[k], dtype)
+    part = low if len(groups) == 1 else torch.empty((len(idx), size, size, 3), dtype=dtype, device=dev)
+    _cabi.bilinear_resize_ragged_codes(cs, tables, stride, center_windows([c.shape[:2] for c in cs]), size, part)
+    if part is not low:
+      low[torch.tensor(idx, device=dev)] = part
+    staged.append((idx, cs, tables, stride))
+  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks)
+  ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
+  mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
+  # the taps of a launch have one format: with storage intermediates the pictures are encoded from the outputs
+  encode = kind and intermediates == 'storage'
+  if kind and not encode:
+    tap_mask, tap_dtype = (mask if intermediates else 0) | last, _CODE_DTYPES[kind]
+  elif intermediates:
+    tap_mask, tap_dtype = mask, _CODE_DTYPES.get(intermediates, dtype)
+  else:
+    tap_mask, tap_dtype = 0, None
+  if encode and not outputs:
+    raise ValueError('retouch_batch_raw: a picture next to storage intermediates is encoded from the output '
+                     '(outputs=False cannot make it)')
+  t = bin(tap_mask).count('1')
+  outs, taps = [None] * n, [None] * n
+  for idx, cs, tables, stride in staged:
+    ys = [torch.empty((1, c.shape[0], c.shape[1], 3), dtype=dtype, device=dev) for c in cs] if outputs else None
+    tp = [torch.empty((t, c.shape[0], c.shape[1], 3), dtype=tap_dtype, device=dev) for c in cs] if t else None
+    sel = torch.tensor(idx, device=dev)
+    whole = len(groups) == 1
+    _cabi.chain_fused_fwd_ragged_codes(ids if whole else ids[sel].contiguous(), prm if whole else prm[sel].contiguous(),
+                                       cs, tables, stride, ys, tap_mask, tp)
+    for j, i in enumerate(idx):
+      if outputs:
+        outs[i] = ys[j]
+      if t:
+        taps[i] = tp[j]
+  res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+  if kind and not encode:
+    if intermediates:
+      res += ([tp if mask & last else tp[:-1] for tp in taps],)
+    return res + ([tp[-1] for tp in taps],)
+  if intermediates:
+    res += (taps,)
+  if encode:
+    res += ([_ENCODERS[kind](o.reshape(o.shape[-3:])) for o in outs],)
+  return res
+
+
 def load_agent_weights(agent, state):
   """Accepts an ``Agent`` state dict, a ``GAN.state_dict()`` (keys prefixed 'generator.' / 'critic.' / 'value.') or the
   ``{'model': GAN.state_dict(), 'optim': ...}`` file that ``python -m exposure_amd.train --save`` writes: the
@@ -629,6 +724,15 @@ def main(argv=None):
                   '(make_low_res_batch) instead of torch\'s interpolate per image.  Same definition, every float32 '
                   'operation rounded on its own: a proxy value can differ from the default path\'s in the last place, '
                   'which in rare cases changes an argmax and with it the chosen filters')
+  ap.add_argument('--fused-decode', action='store_true',
+                  help='retouch straight from the integer codes (retouch_batch_raw): per group of --batch images the '
+                  'device gets the codes as the files hold them, the proxies and the one fused pass gather from the '
+                  "images' tables as they load, and the decoded float input is never made.  The same files and records "
+                  'as --device-decode --device-proxy, which it implies.  Not with --stepwise, --masking or --show-input '
+                  '(the tone-mapped picture needs the float input)')
+  ap.add_argument('--pictures-only', action='store_true',
+                  help='write no .npy: only the pictures (needs --device-png, --tiff16 or --score); the record\'s '
+                  'output is None.  With --fused-decode the float output is not even allocated (outputs=False)')
   ap.add_argument('--device-png', action='store_true',
                   help='write <output>.png from 8-bit values made on the GPU: on the fused paths a tap of the last step '
                   'from the pass that writes the output, with --stepwise an encode of the result.  The same pixels as '
@@ -674,6 +778,13 @@ def main(argv=None):
              'makes pictures of one depth')
   if args.score:
     args.device_png = True
+  if args.fused_decode:
+    if args.stepwise or args.masking or args.show_input:
+      ap.error('--fused-decode does not go with --stepwise, --masking or --show-input: the pass from codes is the '
+               'unmasked fused one, and the tone-mapped picture needs the float input')
+    args.device_decode = args.device_proxy = True
+  if args.pictures_only and not (args.device_png or args.tiff16):
+    ap.error('--pictures-only needs --device-png, --tiff16 or --score: it writes the pictures the device makes')
   if (args.step_by_step and not args.tiff16) or args.device_png:
     args.png = True
   proxy = 'device' if args.device_proxy else 'torch'
@@ -692,8 +803,10 @@ def main(argv=None):
     names = [agent.filters[int(j)].get_short_name() for j in trace[0]]
     print('%s: %dx%d  filters: %s' % (path, hi.shape[2], hi.shape[1], ' '.join(names)))
     dst = output_path(args.out, path, len(args.images) > 1)
-    result = out[0].float().cpu().numpy()
-    np.save(dst, result)
+    result = None
+    if not args.pictures_only:
+      result = out[0].float().cpu().numpy()
+      np.save(dst, result)
     if args.score:
       pictures.append(pic.contiguous())
     pngs, tiffs = {}, {}
@@ -715,7 +828,7 @@ def main(argv=None):
       if inter is not None:
         for i, a in enumerate(inter.cpu().numpy()):
           pngs['intermediate%02d' % i] = save_png_u8('%s.intermediate%02d.png' % (stem, i), a)
-    records.append(dict(image=path, output=dst, png=pngs, tiff=tiffs, filters=names, states=states[0].cpu().tolist(),
+    records.append(dict(image=path, output=None if args.pictures_only else dst, png=pngs, tiff=tiffs, filters=names, states=states[0].cpu().tolist(),
                         abi_filter_ids=ops['abi_filter_ids'][0].cpu().tolist(),
                         params24=ops['params24'][0].cpu().numpy()))
 
@@ -727,7 +840,21 @@ def main(argv=None):
       return decode_images([load_raw(path) for path in paths], dt, dev)
     return [load(path) for path in paths]
 
-  if args.batch == 1 or args.stepwise:
+  def emit_batch(paths, his, res):
+    outs, states, ops = res[0], res[2], res[3]
+    for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
+      emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
+           res[-1][i] if picture else None)
+
+  if args.fused_decode:  # also with --batch 1: groups of one image
+    for b in range(0, len(args.images), args.batch):
+      paths = args.images[b:b + args.batch]
+      raws = [load_raw(path) for path in paths]
+      res = retouch_batch_raw(agent, raws, dt, dev, return_trace='full', intermediates=inter_kind, picture=picture,
+                              outputs=not args.pictures_only)
+      # emit reads of `hi` its size alone here (--show-input is refused): the codes have it
+      emit_batch(paths, [codes[None] for codes, _kind in raws], res)
+  elif args.batch == 1 or args.stepwise:
     for path in args.images:
       hi, = load_group([path])
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
@@ -740,10 +867,7 @@ def main(argv=None):
       his = load_group(paths)
       res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
                           picture=picture, masks=masks)
-      outs, states, ops = res[0], res[2], res[3]
-      for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
-        emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
-             res[-1][i] if picture else None)
+      emit_batch(paths, his, res)
   if args.score:
     import random
     from . import metrics

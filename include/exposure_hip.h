@@ -56,7 +56,9 @@ extern "C" {
                               (expo_fc_*; expo_critic_head_fwd / _bwd take the partial sums); 8: expo_chain_plan;
                               9: expo_chain_fused_fwd_ragged; added exports: the taps, expo_decode_ragged,
                               expo_area_resize_ragged, expo_pack_recut, expo_bilinear_resize_ragged,
-                              expo_patch_stats, expo_stat_hist, expo_chain_fused_masked_fwd_ragged */
+                              expo_patch_stats, expo_stat_hist, expo_chain_fused_masked_fwd_ragged,
+                              expo_decode_tables, expo_bilinear_resize_ragged_codes,
+                              expo_chain_fused_fwd_ragged_codes */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -403,6 +405,52 @@ size_t expo_decode_workspace_bytes(int n, const int* hs, const int* ws, int chan
 int expo_decode_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
                        const float* table, int normalize, void* const* outs, int dtype, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/*
+ * Inference straight from the integer codes: the decode is a table gather, so its consumers can gather at load time
+ * and the decoded float tensor need not exist.  Added exports of ABI 9 (the version is unchanged); every result is
+ * bit-identical to expo_decode_ragged followed by the export that takes tensors.
+ *
+ * expo_decode_tables: the tables expo_decode_ragged uses internally, written into a caller-owned buffer in `dtype`.
+ *   codes, hs, ws, n, channels, code_bits, table, normalize, workspace, workspace_bytes: as expo_decode_ragged
+ *   (normalize 0 reads no codes: codes, hs and ws may be NULL; the workspace is sized by expo_decode_workspace_bytes).
+ *   tables     device buffer, 4-byte aligned, of at least expo_decode_tables_bytes(n, code_bits, normalize, dtype) bytes:
+ *                normalize 1:  n tables, image i's at entry i * 2^code_bits: cast(fl32(table[k] / fl32(2 table[m_i]))),
+ *                              the records, the division and the cast of expo_decode_ragged (alpha not counted).  An image
+ *                              of all-zero codes (2 table[m_i] == 0) gives a table of NaN in every entry: the entries
+ *                              its codes read are 0 / 0 as there, and the others, which no code of the image reads,
+ *                              are NaN too instead of table[k] / 0;
+ *                normalize 0:  ONE shared table cast(table[k]).
+ * Returns the stride between consecutive images' tables in ENTRIES (2^code_bits; 0 = one shared table, and for n == 0,
+ * a no-op), or a negative EXPO_E_* code.  Everything is validated before anything is enqueued, as expo_decode_ragged
+ * does, plus the tables buffer.  expo_decode_tables_bytes is 0 for invalid arguments.
+ *
+ * expo_bilinear_resize_ragged_codes: expo_bilinear_resize_ragged with the windows read from codes: the same windows, S
+ * and individually rounded float32 arithmetic; a tap is float(tables_i[code]), tables in table_dtype.  channels 1 (the
+ * grey channel is replicated), 3 or 4 (alpha is dropped); a code pointer may sit at any byte (uint8) / element (uint16).
+ *   tables, table_stride  what expo_decode_tables wrote and returned: image i's table at entry i * table_stride.
+ * Validated as expo_bilinear_resize_ragged, plus channels, code_bits, table_stride (0 or >= 2^code_bits) and tables.
+ *
+ * expo_chain_fused_fwd_ragged_codes: expo_chain_fused_fwd_ragged_taps with image i's input given as codes[i] plus its
+ * table (in `dtype`, the storage dtype of ys and of storage taps): a pixel value enters the step loop as
+ * float(cast table value), what the decoded tensor would hold.  tap_mask == 0 is allowed (no taps; taps may be NULL);
+ * ys NULL is allowed with taps; ys NULL with tap_mask == 0 is EXPO_E_BADARG.  Every tap_format of the sibling.  64
+ * images per launch by value in the kernel arguments, more as further launches on `stream`.  Per image the vector path is
+ * taken when the codes, y and a vector-stored tap plane are 4-byte aligned and the pixel count is whole 12-byte vectors
+ * (else element-wise).  Validated before anything is enqueued: as the sibling, plus channels, code_bits, table_stride,
+ * tables non-NULL and 4-byte aligned, and the codes of one image smaller than 2 GiB; n == 0 is a no-op.
+ */
+size_t expo_decode_tables_bytes(int n, int code_bits, int normalize, int dtype);
+int expo_decode_tables(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
+                       const float* table, int normalize, void* tables, size_t tables_bytes, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int expo_bilinear_resize_ragged_codes(const void* const* codes, const int* hs, const int* ws, int n, int channels,
+                                      int code_bits, const void* tables, int table_stride, int table_dtype,
+                                      const int32_t* windows, int q, int S, void* out, int out_dtype, void* stream);
+int expo_chain_fused_fwd_ragged_codes(const int32_t* filter_ids, const float* params, int steps,
+                                      const void* const* codes, int channels, int code_bits, const void* tables,
+                                      int table_stride, void* const* ys, const int* hs, const int* ws, int n, int dtype,
+                                      uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
 
 /*
  * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of
