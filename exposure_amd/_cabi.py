@@ -103,6 +103,10 @@ SIGNATURES = {
     'expo_chain_fused_fwd_ragged_codes': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), _i, _i, _vp, _i, ctypes.POINTER(_vp),
                                                ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
                                                ctypes.POINTER(_vp), _vp]),
+    'expo_codes_max_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _vp, _vp, _sz,
+                                   _vp]),
+    'expo_codes_lut_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _vp, _i, _i,
+                                   ctypes.POINTER(_vp), _vp]),
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -897,6 +901,65 @@ def chain_fused_fwd_ragged_codes(filter_ids, params, codes, tables, stride, ys, 
                                                  (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, dtc, tap_mask, fmt,
                                                  None if not t else _ptr_array(taps), _stream()),
            'expo_chain_fused_fwd_ragged_codes')
+
+
+def codes_max_ragged(codes, workspace=None):
+  """``expo_codes_max_ragged``: the largest code of each image over the channels that reach the output (alpha ignored)
+  -> int32 device tensor (N,).  codes as in ``decode_ragged``; the shared workspace serves the call unless
+  ``workspace=`` is given."""
+  lib = load()
+  n = len(codes)
+  if n == 0:
+    raise ExposureHipError('exposure_amd: codes_max_ragged needs at least one image')
+  if not isinstance(codes[0], torch.Tensor) or not codes[0].is_cuda:
+    raise ExposureHipError('exposure_amd: codes must be tensors on a ROCm device (HIP path only, no CPU fallback)')
+  device = codes[0].device
+  bits, c, hs, ws = _codes_args(codes, codes[0].get_device())
+  maxima = torch.empty((n,), dtype=torch.int32, device=device)
+  hsa, wsa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws)
+  with torch.cuda.device(device):
+    need = int(lib.expo_decode_workspace_bytes(n, hsa, wsa, c, bits))
+    if workspace is None:
+      workspace = reserve_workspace(device, need)
+      _order_shared_workspace(device)
+    if not workspace.is_cuda or workspace.device != device or workspace.numel() * workspace.element_size() < need:
+      raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' % (need, device))
+    _check(lib.expo_codes_max_ragged(_ptr_array(codes), hsa, wsa, n, c, bits, _ptr(maxima), _ptr(workspace),
+                                     workspace.numel() * workspace.element_size(), _stream()), 'expo_codes_max_ragged')
+  return maxima
+
+
+def codes_lut_ragged(codes, luts, stride, outs):
+  """``expo_codes_lut_ragged``: outs[i][p][c] = luts[i * stride + codes[i][p][c]] for the 3 output channels (grey
+  replicated, alpha dropped).  codes as in ``decode_ragged``; luts: contiguous uint8 / uint16 device tensor holding image
+  i's 2^bits entries at i * stride (stride 0: one shared table); outs: N contiguous (H_i, W_i, 3) device tensors of the
+  luts' dtype."""
+  lib = load()
+  n = len(codes)
+  if len(outs) != n:
+    raise ExposureHipError('exposure_amd: codes and outs must have the same length')
+  if n == 0:
+    return
+  if not isinstance(luts, torch.Tensor) or not luts.is_cuda or not luts.is_contiguous() or luts.dtype not in _CODE_BITS:
+    raise ExposureHipError('exposure_amd: luts must be a contiguous uint8 / uint16 tensor on a ROCm device')
+  dev, ot = luts.get_device(), luts.dtype
+  bits, c, hs, ws = _codes_args(codes, dev)
+  stride = int(stride)
+  if stride != 0 and stride < (1 << bits):
+    raise ExposureHipError('exposure_amd: lut stride %d is smaller than the %d entries of a table' % (stride, 1 << bits))
+  if luts.numel() < (n - 1) * stride + (1 << bits):
+    raise ExposureHipError('exposure_amd: luts holds %d entries, %d images at stride %d need %d' %
+                           (luts.numel(), n, stride, (n - 1) * stride + (1 << bits)))
+  for i in range(n):
+    y = outs[i]
+    if not isinstance(y, torch.Tensor) or tuple(y.shape) != (hs[i], ws[i], 3) or y.dtype is not ot or \
+        y.get_device() != dev or not y.is_contiguous():
+      raise ExposureHipError('exposure_amd: outs[%d] must be a contiguous (%d, %d, 3) %s tensor on the luts\' device'
+                             % (i, hs[i], ws[i], ot))
+  with torch.cuda.device(dev):
+    _check(lib.expo_codes_lut_ragged(_ptr_array(codes), (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, c, bits,
+                                     _ptr(luts), stride, _CODE_BITS[ot], _ptr_array(outs), _stream()),
+           'expo_codes_lut_ragged')
 
 
 def area_resize_ragged(xs, windows, S, out):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Fourteen translation units; extra arguments go to every compile step.
+# Fifteen translation units; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
@@ -20,6 +20,7 @@
 #                        its definition is rounded on its own, so the host restatement matches bit for bit)
 #   proxy_codes.hip      the same proxies read from the files' integer codes (exactly proxy.hip's flags: it includes that file
 #                        for the arithmetic)
+#   codes_lut.hip        integer pictures gathered from the files' integer codes through caller-built tables (default flags)
 #   metric.hip           the evaluation metric's patch statistics and their histograms (default flags)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -59,6 +60,8 @@ p12=$!
 p13=$!
 "$HIPCC" "${FLAGS[@]}" -ffp-contract=off "$@" -c "$HERE/proxy_codes.hip" -o "$TMP/proxy_codes.o" &
 p14=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/codes_lut.hip" -o "$TMP/codes_lut.o" &
+p15=$!
 wait $p1
 wait $p2
 wait $p3
@@ -73,5 +76,6 @@ wait $p11
 wait $p12
 wait $p13
 wait $p14
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" -o "$OUT"
+wait $p15
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -7,7 +7,7 @@
 // A unit of its own, compiled with exactly chain_fused.hip's flags (csrc/build.sh): it includes that file for
 // chain_fused_run, TapSink and the stores, which it uses untouched, and instantiates none of its kernels
 // (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), so the kernels of chain_fused.hip keep their code and registers and the two units
-// compile side by side.  The only device code of its own is the loader below.
+// compile side by side.  The only device code of its own is the loader below (the row load is codes_loader.h's).
 //   vector path       a lane's group keeps pixel_io.h's pixel positions: row r of a wave's chunk is the 12-byte vector
 //                     of PPV pixels (fp16 2, fp32 1) at pixel gw * PPL + r * 64 * PPV + lane * PPV; its PPV * C codes
 //                     come in with the widest buffer load their size allows, as decode_kernel's.  Rows past the end of
@@ -18,13 +18,11 @@
 //                     16-bit table (128 / 256 KiB per image) is read through the caches.
 #define EXPO_CHAIN_FUSED_TEMPLATES_ONLY
 #include "chain_fused.hip"
+#include "codes_loader.h"
 
 namespace expo {
 
 namespace {
-
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 // up to 64 images by value in the kernel arguments (2 KB): codes, output (NULL: none), tap buffer, pixel count, first
 // block of each image (first[n] = the grid's size) and a bit per image for the vector path
@@ -40,35 +38,6 @@ struct CodesTable {
 };
 // kernel arguments: ids, params, steps, tap_mask, tables, table_stride, the table
 static_assert(sizeof(CodesTable<half_t>) + 48 <= 4096, "the codes table must fit the 4 KB kernarg block");
-
-// the NB = PPV * C * sizeof(CT) code bytes of one lane-row at byte offset off (a multiple of NB; the base is 4-byte
-// aligned), with the widest load their size allows
-template <typename CT, int NB, int AUX>
-__device__ __forceinline__ void load_code_row(__amdgpu_buffer_rsrc_t rin, int off, CT* c) {
-  if constexpr (NB == 16) {
-    const u32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, AUX);
-    __builtin_memcpy(c, &q, NB);
-  } else if constexpr (NB == 12) {
-    const u32x3_t q = __builtin_amdgcn_raw_buffer_load_b96(rin, off, 0, AUX);
-    __builtin_memcpy(c, &q, NB);
-  } else if constexpr (NB == 8) {
-    const u32x2_t q = __builtin_amdgcn_raw_buffer_load_b64(rin, off, 0, AUX);
-    __builtin_memcpy(c, &q, NB);
-  } else if constexpr (NB == 4) {
-    const uint32_t q = __builtin_amdgcn_raw_buffer_load_b32(rin, off, 0, AUX);
-    __builtin_memcpy(c, &q, NB);
-  } else if constexpr (NB % 2 == 0) {  // 2 or 6 bytes: 2-byte aligned
-    uint16_t q[NB / 2];
-#pragma unroll
-    for (int k = 0; k < NB / 2; ++k) q[k] = __builtin_amdgcn_raw_buffer_load_b16(rin, off + 2 * k, 0, AUX);
-    __builtin_memcpy(c, q, NB);
-  } else {  // 1 or 3 bytes
-    uint8_t q[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) q[k] = __builtin_amdgcn_raw_buffer_load_b8(rin, off + k, 0, AUX);
-    __builtin_memcpy(c, q, NB);
-  }
-}
 
 // chain_fused_image_taps with the codes loader; Sink = NoSink: no taps.  look(code) is the table gather.  yi may be
 // NULL with taps.  One chunk per wave and trip, the next trip `stride` groups on (the ragged grid covers an image's

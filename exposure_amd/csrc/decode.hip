@@ -15,6 +15,8 @@
 // decode_finish_kernel as above, the finish writing into the caller's buffer, or decode_cast_kernel for the one shared
 // table T(table[k]) of a call without normalisation.  Their consumers gather at load time (proxy.hip,
 // chain_fused_codes.hip).
+// expo_codes_max_ragged stops after the maxima: decode_max_kernel, then codes_max_finish_kernel
+// writing each image's largest code as an int32 -- the m_i above, also for calls that never normalise.
 #include <limits.h>
 
 #include "host_common.h"
@@ -141,6 +143,16 @@ __global__ __launch_bounds__(kThreads) void decode_finish_kernel(const DecodeTab
   const int e0 = blockIdx.x * kFinishEntries;
   const int e1 = min(entries, e0 + kFinishEntries);
   for (int e = e0 + threadIdx.x; e < e1; e += kThreads) tj[e] = T(table[e] / d);
+}
+
+// expo_codes_max_ragged's finish, one block per image: image j's largest record, as an int32
+__global__ __launch_bounds__(kThreads) void codes_max_finish_kernel(const DecodeTable tab, const uint32_t* __restrict__ records,
+                                                                    int32_t* __restrict__ maxima) {
+  const int j = blockIdx.x;
+  uint32_t m = 0;
+  for (int r = tab.first[j] + threadIdx.x; r < tab.first[j + 1]; r += kThreads) m = max(m, records[r]);
+  m = block_max(m);
+  if (threadIdx.x == 0) maxima[j] = int32_t(m);
 }
 
 // the shared table of a call without normalisation, in the storage dtype
@@ -361,6 +373,50 @@ int decode_tables_t(const void* const* codes, const int* hs, const int* ws, int 
   return EXPO_OK;
 }
 
+// arguments validated by the caller: decode_max_kernel's records of a launch in the workspace (launches reuse it in
+// stream order), then the finish into maxima
+template <typename CT, int C>
+int codes_max_t(const void* const* codes, const int* hs, const int* ws, int n, int32_t* maxima, void* workspace,
+                hipStream_t s) {
+  long bytes = 0;
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * C * long(sizeof(CT));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kDecodeMaxImages) {
+    const int m = n - base < kDecodeMaxImages ? n - base : kDecodeMaxImages;
+    DecodeTable mt = {};
+    mt.n = m;
+    long mblocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      mt.codes[j] = codes[i];
+      mt.hw[j] = hw;
+      mt.first[j] = int(mblocks);
+      mblocks += max_blocks(long(hw) * C * long(sizeof(CT)));
+      if ((reinterpret_cast<uintptr_t>(codes[i]) & 3) == 0) mt.vec |= uint64_t(1) << j;
+    }
+    if (mblocks > INT_MAX) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    mt.first[m] = int(mblocks);
+    const dim3 block(kThreads);
+    uint32_t* rec = static_cast<uint32_t*>(workspace);
+    if (stream)
+      hipLaunchKernelGGL((decode_max_kernel<CT, C, IoStream>), dim3(unsigned(mblocks)), block, 0, s, mt, rec);
+    else
+      hipLaunchKernelGGL((decode_max_kernel<CT, C, IoCached>), dim3(unsigned(mblocks)), block, 0, s, mt, rec);
+    HIP_TRY(hipGetLastError(), "decode_max launch");
+    hipLaunchKernelGGL(codes_max_finish_kernel, dim3(unsigned(m)), block, 0, s, mt, rec, maxima + base);
+    HIP_TRY(hipGetLastError(), "codes_max_finish launch");
+  }
+  return EXPO_OK;
+}
+
+template <typename CT>
+int codes_max_channels(int channels, const void* const* codes, const int* hs, const int* ws, int n, int32_t* maxima,
+                       void* workspace, hipStream_t s) {
+  if (channels == 1) return codes_max_t<CT, 1>(codes, hs, ws, n, maxima, workspace, s);
+  if (channels == 3) return codes_max_t<CT, 3>(codes, hs, ws, n, maxima, workspace, s);
+  return codes_max_t<CT, 4>(codes, hs, ws, n, maxima, workspace, s);
+}
+
 template <typename CT, typename T>
 int decode_tables_channels(int channels, const void* const* codes, const int* hs, const int* ws, int n,
                            const float* table, void* tables, void* workspace, hipStream_t s) {
@@ -484,6 +540,31 @@ int expo_decode_tables(const void* const* codes, const int* hs, const int* ws, i
     rc = dtype == EXPO_F16 ? decode_tables_channels<uint16_t, half_t>(channels, codes, hs, ws, n, table, tables, workspace, s)
                            : decode_tables_channels<uint16_t, float>(channels, codes, hs, ws, n, table, tables, workspace, s);
   return rc != EXPO_OK ? rc : 1 << code_bits;
+}
+
+int expo_codes_max_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
+                          int32_t* maxima, void* workspace, size_t workspace_bytes, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (channels != 1 && channels != 3 && channels != 4) return fail(EXPO_E_BADARG, "channels must be 1, 3 or 4");
+  if (code_bits != 8 && code_bits != 16) return fail(EXPO_E_BADARG, "code_bits must be 8 or 16");
+  if (n == 0) return EXPO_OK;
+  if (!codes || !hs || !ws || !maxima) return fail(EXPO_E_BADARG, "null pointer");
+  if ((reinterpret_cast<uintptr_t>(maxima) & 3) != 0) return fail(EXPO_E_BADARG, "maxima must be 4-byte aligned");
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], EXPO_F16)) return rc;
+    if (long(hs[i]) * ws[i] * channels * (code_bits / 8) > (1L << 31) - 8192)
+      return fail(EXPO_E_BADARG, "the codes of one image must be smaller than 2 GiB");
+    if (!codes[i]) return fail(EXPO_E_BADARG, "null image pointer");
+  }
+  const long need = workspace_need(n, hs, ws, channels, code_bits);
+  if (need < 0) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
+    return fail(EXPO_E_BADARG, "a 4-byte aligned workspace is needed");
+  if (workspace_bytes < size_t(need)) return fail(EXPO_E_BADARG, "workspace too small (expo_decode_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (code_bits == 8) return codes_max_channels<uint8_t>(channels, codes, hs, ws, n, maxima, workspace, s);
+  return codes_max_channels<uint16_t>(channels, codes, hs, ws, n, maxima, workspace, s);
 }
 
 }  // extern "C"

@@ -481,27 +481,6 @@ def decode_table(kind, device):
   return t
 
 
-def decode_images(raws, dtype, device):
-  """``load_image`` + ``.to(dtype)`` on the device from ``load_raw`` results: the codes are uploaded as they are and
-  ``_cabi.decode_ragged`` makes the linear storage tensors, bit for bit what the host path gives.  One ragged call
-  per distinct (kind, channels); returns (1, H, W, 3) tensors in the order of ``raws``."""
-  from . import _cabi
-  dev = torch.device(device)
-  outs = [None] * len(raws)
-  groups = {}
-  for i, (codes, kind) in enumerate(raws):
-    groups.setdefault((kind, codes.shape[2]), []).append(i)
-  for (kind, _c), idx in groups.items():
-    with warnings.catch_warnings():  # PIL's arrays are read-only: they are only read, by the upload
-      warnings.simplefilter('ignore', UserWarning)
-      cs = [torch.from_numpy(np.ascontiguousarray(raws[i][0])).to(dev) for i in idx]
-    ys = [torch.empty((1, c.shape[0], c.shape[1], 3), dtype=dtype, device=dev) for c in cs]
-    _cabi.decode_ragged(cs, decode_table(kind, dev), DECODE_NORMALIZE[kind], ys)
-    for i, y in zip(idx, ys):
-      outs[i] = y
-  return outs
-
-
 def upload_codes(codes, device):
   """The codes of one ``load_raw`` result on the device, as they are (PIL's arrays are read-only: they are only read)."""
   with warnings.catch_warnings():
@@ -509,14 +488,52 @@ def upload_codes(codes, device):
     return torch.from_numpy(np.ascontiguousarray(codes)).to(device)
 
 
+def decode_images(raws, dtype, device, staged=None):
+  """``load_image`` + ``.to(dtype)`` on the device from ``load_raw`` results: the codes are uploaded as they are and
+  ``_cabi.decode_ragged`` makes the linear storage tensors, bit for bit what the host path gives.  One ragged call
+  per distinct (kind, channels); returns (1, H, W, 3) tensors in the order of ``raws``.  ``staged``: the listed result
+  of ``stage_raws`` for these ``raws``; its uploaded codes are decoded instead of a second upload."""
+  from . import _cabi
+  dev = torch.device(device)
+  outs = [None] * len(raws)
+  if staged is None:
+    groups = {}
+    for i, (codes, kind) in enumerate(raws):
+      groups.setdefault((kind, codes.shape[2]), []).append(i)
+    staged = ((idx, [upload_codes(raws[i][0], dev) for i in idx], None, None, kind) for (kind, _c), idx in groups.items())
+  for idx, cs, _tables, _stride, kind in staged:
+    ys = [torch.empty((1, c.shape[0], c.shape[1], 3), dtype=dtype, device=dev) for c in cs]
+    _cabi.decode_ragged(cs, decode_table(kind, dev), DECODE_NORMALIZE[kind], ys)
+    for i, y in zip(idx, ys):
+      outs[i] = y
+  return outs
+
+
+def stage_raws(raws, dtype, device):
+  """The upload-and-tables staging the passes from codes share: per (kind, channels) group of ``raws`` (``load_raw``
+  results), in order of first appearance, yields (the images' indices, their codes on the device, the tables
+  ``decode_ragged`` would gather from in ``dtype``, the tables' stride, the kind).  A generator: a consumer may work on
+  a group before the next one is staged; ``list(stage_raws(...))`` can be handed to ``retouch_batch_raw`` and
+  ``input_pictures_raw`` (``staged=``), so the codes are uploaded once for both."""
+  from . import _cabi
+  dev = torch.device(device)
+  groups = {}
+  for i, (codes, k) in enumerate(raws):
+    groups.setdefault((k, codes.shape[2]), []).append(i)
+  for (k, _c), idx in groups.items():
+    cs = [upload_codes(raws[i][0], dev) for i in idx]
+    tables, stride = _cabi.decode_tables(cs, decode_table(k, dev), DECODE_NORMALIZE[k], dtype)
+    yield idx, cs, tables, stride, k
+
+
 @torch.no_grad()
 def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_masks=None, return_trace=False,
-                      intermediates=None, picture=False, outputs=True):
+                      intermediates=None, picture=False, outputs=True, staged=None):
   """``retouch_batch(agent, decode_images(raws, dtype, device), proxy='device', ...)`` without the decoded tensors
   (DESIGN.md §3.23): ``raws`` are ``load_raw`` results, and the integer codes are what the device reads.  Per
-  (kind, channels) group of the batch ``_cabi.decode_tables`` writes the tables ``decode_ragged`` would gather from;
-  then the 64x64 proxies of the whole batch, stacked in argument order, come from one
-  ``_cabi.bilinear_resize_ragged_codes`` call per group, the agent runs once, and one
+  (kind, channels) group of the batch ``_cabi.decode_tables`` writes the tables ``decode_ragged`` would gather from
+  (``stage_raws``; ``staged=`` takes its listed result instead); then the 64x64 proxies of the whole batch, stacked in
+  argument order, come from one ``_cabi.bilinear_resize_ragged_codes`` call per group, the agent runs once, and one
   ``_cabi.chain_fused_fwd_ragged_codes`` launch per group applies that group's rows of ids and params to the codes.
   Every returned value is bit for bit the one of the call above.
 
@@ -543,20 +560,15 @@ def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_ma
   steps = steps or cfg.test_steps
   if z is None:
     z = torch.rand((n, cfg.z_dim), device=dev)
-  groups = {}
-  for i, (codes, k) in enumerate(raws):
-    groups.setdefault((k, codes.shape[2]), []).append(i)
   size = cfg.source_img_size
   low = torch.empty((n, size, size, 3), dtype=dtype, device=dev)
-  staged = []  # per group: the images' indices, their codes on the device, the tables and their stride
-  for (k, _c), idx in groups.items():
-    cs = [upload_codes(raws[i][0], dev) for i in idx]
-    tables, stride = _cabi.decode_tables(cs, decode_table(k, dev), DECODE_NORMALIZE[k], dtype)
-    part = low if len(groups) == 1 else torch.empty((len(idx), size, size, 3), dtype=dtype, device=dev)
+  groups = []  # per group: the images' indices, their codes on the device, the tables and their stride
+  for idx, cs, tables, stride, _k in (stage_raws(raws, dtype, dev) if staged is None else staged):
+    part = low if len(idx) == n else torch.empty((len(idx), size, size, 3), dtype=dtype, device=dev)
     _cabi.bilinear_resize_ragged_codes(cs, tables, stride, center_windows([c.shape[:2] for c in cs]), size, part)
     if part is not low:
       low[torch.tensor(idx, device=dev)] = part
-    staged.append((idx, cs, tables, stride))
+    groups.append((idx, cs, tables, stride))
   low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks)
   ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
   mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
@@ -573,11 +585,11 @@ def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_ma
                      '(outputs=False cannot make it)')
   t = bin(tap_mask).count('1')
   outs, taps = [None] * n, [None] * n
-  for idx, cs, tables, stride in staged:
+  for idx, cs, tables, stride in groups:
     ys = [torch.empty((1, c.shape[0], c.shape[1], 3), dtype=dtype, device=dev) for c in cs] if outputs else None
     tp = [torch.empty((t, c.shape[0], c.shape[1], 3), dtype=tap_dtype, device=dev) for c in cs] if t else None
     sel = torch.tensor(idx, device=dev)
-    whole = len(groups) == 1
+    whole = len(idx) == n
     _cabi.chain_fused_fwd_ragged_codes(ids if whole else ids[sel].contiguous(), prm if whole else prm[sel].contiguous(),
                                        cs, tables, stride, ys, tap_mask, tp)
     for j, i in enumerate(idx):
@@ -595,6 +607,74 @@ def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_ma
   if encode:
     res += ([_ENCODERS[kind](o.reshape(o.shape[-3:])) for o in outs],)
   return res
+
+
+INPUT_CODES = {'u8': (np.uint8, 255.0), 'u16': (np.uint16, 65535.0)}
+
+
+def input_luts(tables, stride, maxima, code='u8'):
+  """The integer tables of the reference's two input pictures (``GAN.eval``, ``net.py:825-839``) over the code range,
+  per image: (linear, tone_mapped), two (N, 2^bits) NumPy arrays of uint8 (``code='u8'``) or uint16 (``'u16'``).
+  ``tables`` / ``stride`` are what ``_cabi.decode_tables`` returned (the storage-dtype tables, image i's row at entry
+  i * stride; stride 0: one shared row), ``maxima`` the N largest codes of ``_cabi.codes_max_ragged``.  With
+  t = float32(table of image i) -- the values the decoded image holds, code by code -- the tables are the project's own
+  host expressions evaluated on t:
+    linear       ``save_png``'s encoding of t                                     clip(rint(t * 255))
+    tone_mapped  ``save_png``'s encoding of ``tone_mapped_input``'s expression    clip(rint((t / t[m_i]) ** (1 / 2.4) * 255))
+  with ``a.max()`` = t[m_i]: the tables are non-decreasing, so the decoded image's largest value sits at its largest
+  code.  ``'u16'`` uses ``encode_u16``'s scale 65535 instead of 255.  A picture is then a gather by code
+  (``_cabi.codes_lut_ragged``), bit for bit ``save_png``'s encoding of the decoded image's pictures.
+
+  An image whose divisor t[m_i] is 0 or NaN -- all-zero codes: the reference divides by zero there, and a normalised
+  table is NaN throughout -- gets tables of 0 for both pictures."""
+  ct, scale = INPUT_CODES[code]
+  t = tables.detach().float().cpu().numpy()
+  t = t.reshape(-1, t.shape[-1])
+  m = np.asarray(maxima.cpu() if isinstance(maxima, torch.Tensor) else maxima).astype(np.int64).reshape(-1)
+  entries = t.shape[-1]
+  lin = np.zeros((len(m), entries), dtype=ct)
+  tone = np.zeros((len(m), entries), dtype=ct)
+  top = float(np.iinfo(ct).max)
+  for i, mi in enumerate(m):
+    a = t[(i * int(stride)) // entries]
+    d = a[mi]
+    if d == 0 or np.isnan(d):
+      continue
+    lin[i] = np.clip(np.rint(a * scale), 0, top).astype(ct)
+    tone[i] = np.clip(np.rint(((a / d)**(1 / 2.4)) * scale), 0, top).astype(ct)
+  return lin, tone
+
+
+@torch.no_grad()
+def input_pictures_raw(raws, dtype, device, linear=True, tone_mapped=True, code='u8', staged=None):
+  """The reference's ``linear`` and ``input_tone_mapped`` pictures of ``load_raw`` results, made on the device from the
+  integer codes: per (kind, channels) group one ``_cabi.codes_max_ragged``, the group's tables from
+  ``input_luts`` uploaded, and one ``_cabi.codes_lut_ragged`` per requested picture kind.  Returns one list per requested
+  kind, in the order (linear, tone_mapped): N device tensors (H_i, W_i, 3) of uint8 (``code='u8'``) or uint16, in the
+  order of ``raws``; each equals ``save_png``'s encoding (``'u16'``: ``encode_u16``'s) of the decoded input, or of
+  ``tone_mapped_input`` of it, in every value.  No float image exists at any point.  ``staged`` as in
+  ``retouch_batch_raw``; ``dtype`` is the storage dtype the pictures are those of."""
+  from . import _cabi
+  if code not in INPUT_CODES:
+    raise ValueError('code must be one of %s' % (tuple(INPUT_CODES),))
+  raws = list(raws)
+  n = len(raws)
+  if n == 0:
+    raise ValueError('input_pictures_raw: no images')
+  if not (linear or tone_mapped):
+    raise ValueError('input_pictures_raw: nothing requested (linear and tone_mapped both False)')
+  dev = torch.device(device)
+  want = [name for name, on in (('linear', linear), ('tone_mapped', tone_mapped)) if on]
+  pics = {name: [None] * n for name in want}
+  for idx, cs, tables, stride, _k in (stage_raws(raws, dtype, dev) if staged is None else staged):
+    luts = dict(zip(('linear', 'tone_mapped'), input_luts(tables, stride, _cabi.codes_max_ragged(cs), code)))
+    for name in want:
+      lut = torch.from_numpy(luts[name]).to(dev)
+      outs = [torch.empty((c.shape[0], c.shape[1], 3), dtype=lut.dtype, device=dev) for c in cs]
+      _cabi.codes_lut_ragged(cs, lut, lut.shape[1], outs)
+      for i, o in zip(idx, outs):
+        pics[name][i] = o
+  return tuple(pics[name] for name in want)
 
 
 def load_agent_weights(agent, state):
@@ -643,7 +723,8 @@ def _host_codes(t):
 
 def tone_mapped_input(linear):
   """``net.py:822-823``: max to white, then gamma 1/2.4 -- the ``input_tone_mapped`` picture of ``GAN.eval``.  Host
-  maths also with ``--device-png``: a device ``pow`` cannot be made bit-identical to numpy's."""
+  maths also with ``--device-png``: a device ``pow`` cannot be made bit-identical to numpy's.  (``input_pictures_raw``
+  makes the same picture on the device without one: this expression over the code range, then a gather.)"""
   a = np.asarray(linear, dtype=np.float32)
   return (a / a.max())**(1 / 2.4)
 
@@ -696,6 +777,14 @@ def main(argv=None):
                   help="also write <output>.png (8-bit, the reference's `<name>.retouched.png`, net.py:769-772, 832) "
                   'and, with --show-input, <output>.input_tone_mapped.png (net.py:822-829)')
   ap.add_argument('--show-input', action='store_true')
+  ap.add_argument('--show-linear', action='store_true',
+                  help="also write <output>.linear.png, the 8-bit picture of the linear input (GAN.eval's `linear`, "
+                  'net.py:825-839); wherever --show-input works')
+  ap.add_argument('--device-input-png', action='store_true',
+                  help="make --show-input's and --show-linear's pictures on the GPU from the integer codes "
+                  '(input_pictures_raw): the host evaluates its own expressions on the code range, the device gathers; the '
+                  'same PNG bytes as the host path, without the float download and the full-size pow.  Implies '
+                  '--device-decode; the pictures are 8-bit PNGs, also with --tiff16')
   ap.add_argument('--step-by-step', action='store_true',
                   help="also write <output>.intermediateNN.png, the picture after every step but the last (evaluate.py:31, "
                   'net.py:820-823); implies --png.  The fused paths write them from the same pass as 8-bit values')
@@ -728,8 +817,8 @@ def main(argv=None):
                   help='retouch straight from the integer codes (retouch_batch_raw): per group of --batch images the '
                   'device gets the codes as the files hold them, the proxies and the one fused pass gather from the '
                   "images' tables as they load, and the decoded float input is never made.  The same files and records "
-                  'as --device-decode --device-proxy, which it implies.  Not with --stepwise, --masking or --show-input '
-                  '(the tone-mapped picture needs the float input)')
+                  'as --device-decode --device-proxy, which it implies.  Not with --stepwise or --masking; '
+                  '--show-input / --show-linear need --device-input-png (the host pictures need the float input)')
   ap.add_argument('--pictures-only', action='store_true',
                   help='write no .npy: only the pictures (needs --device-png, --tiff16 or --score); the record\'s '
                   'output is None.  With --fused-decode the float output is not even allocated (outputs=False)')
@@ -779,10 +868,12 @@ def main(argv=None):
   if args.score:
     args.device_png = True
   if args.fused_decode:
-    if args.stepwise or args.masking or args.show_input:
+    if args.stepwise or args.masking or ((args.show_input or args.show_linear) and not args.device_input_png):
       ap.error('--fused-decode does not go with --stepwise, --masking or --show-input: the pass from codes is the '
                'unmasked fused one, and the tone-mapped picture needs the float input')
     args.device_decode = args.device_proxy = True
+  if args.device_input_png:
+    args.device_decode = True
   if args.pictures_only and not (args.device_png or args.tiff16):
     ap.error('--pictures-only needs --device-png, --tiff16 or --score: it writes the pictures the device makes')
   if (args.step_by_step and not args.tiff16) or args.device_png:
@@ -795,10 +886,27 @@ def main(argv=None):
   records = []
   pictures = []  # --score: every emitted image's uint8 picture, kept on the device (not the float outputs)
 
-  def emit(path, hi, out, states, ops, inter=None, pic=None):
+  show = [name for name, on in (('linear', args.show_linear), ('input_tone_mapped', args.show_input)) if on]
+
+  def input_pictures(raws, staged=None):
+    """--device-input-png: per image the requested input pictures as uint8 device tensors, by name (else None)"""
+    if not (args.device_input_png and show):
+      return None
+    made = input_pictures_raw(raws, dt, dev, linear=args.show_linear, tone_mapped=args.show_input, staged=staged)
+    return [dict(zip(show, per)) for per in zip(*made)]
+
+  def save_input_pngs(pngs, stem, hi, inp):
+    for name in show:
+      if inp is not None:
+        pngs[name] = save_png_u8('%s.%s.png' % (stem, name), inp[name].cpu().numpy())
+      else:
+        a = hi[0].float().cpu().numpy()
+        pngs[name] = save_png('%s.%s.png' % (stem, name), tone_mapped_input(a) if name == 'input_tone_mapped' else a)
+
+  def emit(path, hi, out, states, ops, inter=None, pic=None, inp=None):
     """print, save and record one image's result (hi, out: (1, H, W, 3); states, ops: that image's rows; inter: its
     (S-1, H, W, 3) uint8 / uint16 intermediates with --step-by-step; pic: its (H, W, 3) uint8 picture with
-    --device-png, uint16 with --tiff16)"""
+    --device-png, uint16 with --tiff16; inp: its input pictures with --device-input-png)"""
     trace = ops['selected']
     names = [agent.filters[int(j)].get_short_name() for j in trace[0]]
     print('%s: %dx%d  filters: %s' % (path, hi.shape[2], hi.shape[1], ' '.join(names)))
@@ -813,8 +921,7 @@ def main(argv=None):
     stem = dst[:-4] if dst.endswith('.npy') else dst
     if args.tiff16:
       tiffs['retouched'] = save_tiff_u16(stem + '.tif', _host_codes(pic))
-      if args.show_input:
-        pngs['input_tone_mapped'] = save_png(stem + '.input_tone_mapped.png', tone_mapped_input(hi[0].float().cpu().numpy()))
+      save_input_pngs(pngs, stem, hi, inp)
       if inter is not None:
         for i, a in enumerate(_host_codes(inter)):
           tiffs['intermediate%02d' % i] = save_tiff_u16('%s.intermediate%02d.tif' % (stem, i), a)
@@ -823,8 +930,7 @@ def main(argv=None):
         pngs['retouched'] = save_png_u8(stem + '.png', pic.cpu().numpy())
       else:
         pngs['retouched'] = save_png(stem + '.png', result)
-      if args.show_input:
-        pngs['input_tone_mapped'] = save_png(stem + '.input_tone_mapped.png', tone_mapped_input(hi[0].float().cpu().numpy()))
+      save_input_pngs(pngs, stem, hi, inp)
       if inter is not None:
         for i, a in enumerate(inter.cpu().numpy()):
           pngs['intermediate%02d' % i] = save_png_u8('%s.intermediate%02d.png' % (stem, i), a)
@@ -836,38 +942,44 @@ def main(argv=None):
     return torch.from_numpy(np.ascontiguousarray(load_image(path))).to(dev).to(dt)[None]
 
   def load_group(paths):
+    """-> the images, and per image its device-made input pictures (None without --device-input-png)"""
     if args.device_decode:
-      return decode_images([load_raw(path) for path in paths], dt, dev)
-    return [load(path) for path in paths]
+      raws = [load_raw(path) for path in paths]
+      if args.device_input_png and show:  # the codes go up once, for the decode and for the input pictures
+        staged = list(stage_raws(raws, dt, dev))
+        return decode_images(raws, dt, dev, staged), input_pictures(raws, staged)
+      return decode_images(raws, dt, dev), None
+    return [load(path) for path in paths], None
 
-  def emit_batch(paths, his, res):
+  def emit_batch(paths, his, res, inps=None):
     outs, states, ops = res[0], res[2], res[3]
     for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
       emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
-           res[-1][i] if picture else None)
+           res[-1][i] if picture else None, inps[i] if inps else None)
 
   if args.fused_decode:  # also with --batch 1: groups of one image
     for b in range(0, len(args.images), args.batch):
       paths = args.images[b:b + args.batch]
       raws = [load_raw(path) for path in paths]
+      staged = list(stage_raws(raws, dt, dev))  # the codes go up once, for the pass and for the input pictures
       res = retouch_batch_raw(agent, raws, dt, dev, return_trace='full', intermediates=inter_kind, picture=picture,
-                              outputs=not args.pictures_only)
-      # emit reads of `hi` its size alone here (--show-input is refused): the codes have it
-      emit_batch(paths, [codes[None] for codes, _kind in raws], res)
+                              outputs=not args.pictures_only, staged=staged)
+      # emit reads of `hi` its size alone here (the input pictures come from the codes): the codes have it
+      emit_batch(paths, [codes[None] for codes, _kind in raws], res, input_pictures(raws, staged))
   elif args.batch == 1 or args.stepwise:
     for path in args.images:
-      hi, = load_group([path])
+      (hi,), inps = load_group([path])
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
                     picture=picture, masks=masks)
       emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None,
-           res[-1][0] if picture else None)
+           res[-1][0] if picture else None, inps[0] if inps else None)
   else:
     for b in range(0, len(args.images), args.batch):
       paths = args.images[b:b + args.batch]
-      his = load_group(paths)
+      his, inps = load_group(paths)
       res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
                           picture=picture, masks=masks)
-      emit_batch(paths, his, res)
+      emit_batch(paths, his, res, inps)
   if args.score:
     import random
     from . import metrics

@@ -58,7 +58,8 @@ extern "C" {
                               expo_area_resize_ragged, expo_pack_recut, expo_bilinear_resize_ragged,
                               expo_patch_stats, expo_stat_hist, expo_chain_fused_masked_fwd_ragged,
                               expo_decode_tables, expo_bilinear_resize_ragged_codes,
-                              expo_chain_fused_fwd_ragged_codes */
+                              expo_chain_fused_fwd_ragged_codes, expo_codes_max_ragged,
+                              expo_codes_lut_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -451,6 +452,32 @@ int expo_chain_fused_fwd_ragged_codes(const int32_t* filter_ids, const float* pa
                                       const void* const* codes, int channels, int code_bits, const void* tables,
                                       int table_stride, void* const* ys, const int* hs, const int* ws, int n, int dtype,
                                       uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
+
+/*
+ * The input pictures from the integer codes.  Added exports of ABI 9 (the version is unchanged).
+ *
+ * expo_codes_max_ragged: maxima[i] (device int32 [n]) = the largest code of image i over the channels that reach the
+ * output (alpha ignored; the one channel when channels == 1): the m_i expo_decode_ragged normalises by.
+ *   workspace  caller-owned, 4-byte aligned device scratch of at least expo_decode_workspace_bytes(...) bytes.
+ * Validated before anything is enqueued, as expo_decode_ragged with normalize 1; n == 0 is a no-op.
+ *
+ * expo_codes_lut_ragged: outs[i][p][c] = luts[i * lut_stride + code_i(p, c)] for the 3 output channels (grey is
+ * replicated, alpha is dropped).
+ *   luts       device array of uint8 (out_bits 8) or uint16 (out_bits 16) entries; with out_bits 16, 2-byte aligned.
+ *   lut_stride 0 (one shared table) or at least 2^code_bits entries between consecutive images' tables.
+ *   outs       HOST array of n device pointers to [hs[i]][ws[i]][3] integers of out_bits.
+ * A code pointer may start at any byte (uint8) or element (uint16), and so may an output pointer.  Per image the vector
+ * path is taken when codes and output are 4-byte aligned and the pixel count is a multiple of 4 (else element-wise).
+ * 8-bit tables are staged in LDS.  16-bit codes with uint8 entries and 16-byte aligned tables stage their 64 KiB table
+ * in LDS too; every other 16-bit case reads the table through the caches.  The environment variable
+ * EXPO_CODES_LUT_LDS16, read at every call, set to 0 makes all 16-bit codes read through the caches (1 or unset: the
+ * default above); the values written are the same.  64 images
+ * per launch, more as further launches on `stream`.  Everything is validated before anything is enqueued; n == 0 is a no-op.
+ */
+int expo_codes_max_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
+                          int32_t* maxima, void* workspace, size_t workspace_bytes, void* stream);
+int expo_codes_lut_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
+                          const void* luts, int lut_stride, int out_bits, void* const* outs, void* stream);
 
 /*
  * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of
