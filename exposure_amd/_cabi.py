@@ -21,6 +21,7 @@ EXPO_ABI_VERSION = 9
 EXPO_CURVE_MAX_STEPS = 16
 EXPO_F16, EXPO_F32 = 0, 1
 EXPO_MAX_PARAMS = 24
+EXPO_MAX_PARAMS_CURVES = 48  # a row of chain_fused_curves_fwd_ragged: 3 x EXPO_CURVE_MAX_STEPS
 EXPO_TAP_STORAGE, EXPO_TAP_U8 = 0, 1
 EXPO_TAP_U16 = 3
 NUM_PARAMS = (1, 1, 3, 1, 8, 1, 1, 24, 2)  # ids 0..7 = cfg.filters order, 8 = LevelFilter
@@ -90,6 +91,9 @@ SIGNATURES = {
                                               ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
                                               ctypes.POINTER(_vp), _vp]),
     'expo_chain_fused_masked_fwd_ragged': (_i, [_vp, _fp, _fp, _i, _f, _f, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
+                                                ctypes.POINTER(_vp), _vp]),
+    'expo_chain_fused_curves_fwd_ragged': (_i, [_vp, _fp, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                                 ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
                                                 ctypes.POINTER(_vp), _vp]),
     'expo_decode_workspace_bytes': (_sz, [_i, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
@@ -591,9 +595,9 @@ def chain_fused_fwd_taps(filter_ids, params, x, y, tap_mask, taps):
            'expo_chain_fused_fwd_taps')
 
 
-def _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps):
+def _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps, width=EXPO_MAX_PARAMS):
   """The checks the ragged calls with taps share, a few attribute reads per image: -> (steps, device, tap format, hs,
-  ws), or None for an empty list."""
+  ws), or None for an empty list.  `width`: the floats of a parameter row."""
   n = len(xs)
   if ys is not None and len(ys) != n:
     raise ExposureHipError('exposure_amd: xs and ys must have the same length')
@@ -603,7 +607,7 @@ def _ragged_tap_args(filter_ids, params, xs, ys, tap_mask, taps):
       not filter_ids.is_contiguous():
     raise ExposureHipError('exposure_amd: filter_ids must be a contiguous int32 device tensor of shape (N, steps)')
   steps = filter_ids.shape[1]
-  _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
+  _f32(params, 'params', (n, steps, width))
   t = _tap_count(tap_mask, steps)
   if n == 0:
     return None
@@ -683,6 +687,30 @@ def chain_fused_masked_fwd_ragged(filter_ids, params, mask_params, xs, ys, maxim
                                                   (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]), tap_mask, fmt,
                                                   None if taps is None else _ptr_array(taps), _stream()),
            'expo_chain_fused_masked_fwd_ragged')
+
+
+def chain_fused_curves_fwd_ragged(filter_ids, params48, curve_steps, xs, ys, tap_mask=0, taps=None):
+  """``chain_fused_fwd_ragged_taps`` for any cfg.curve_steps (``expo_chain_fused_curves_fwd_ragged``): params48
+  (N, steps, EXPO_MAX_PARAMS_CURVES) float32, a Tone row k_0..k_{L-1}, a Color row channel * L + knot, every other
+  filter's values at the front of its row; curve_steps = L in [1, EXPO_CURVE_MAX_STEPS].  xs, ys, tap_mask and taps as
+  in ``chain_fused_fwd_ragged_taps``, with the same per-image checks."""
+  lib = load()
+  curve_steps = int(curve_steps)
+  if not 1 <= curve_steps <= EXPO_CURVE_MAX_STEPS:
+    raise ExposureHipError('exposure_amd: curve_steps must be in [1, %d], got %d' % (EXPO_CURVE_MAX_STEPS, curve_steps))
+  if ys is None and not tap_mask:
+    raise ExposureHipError('exposure_amd: nothing to write (ys None and tap_mask 0)')
+  args = _ragged_tap_args(filter_ids, params48, xs, ys, tap_mask, taps, EXPO_MAX_PARAMS_CURVES)
+  if args is None:
+    return
+  steps, dev, fmt, hs, ws = args
+  n = len(xs)
+  with torch.cuda.device(dev):
+    _check(lib.expo_chain_fused_curves_fwd_ragged(_ptr(filter_ids), _ptr(params48), steps, curve_steps, _ptr_array(xs),
+                                                  None if ys is None else _ptr_array(ys), (ctypes.c_int * n)(*hs),
+                                                  (ctypes.c_int * n)(*ws), n, _dtype_code(xs[0]), tap_mask, fmt,
+                                                  None if taps is None else _ptr_array(taps), _stream()),
+           'expo_chain_fused_curves_fwd_ragged')
 
 
 def decode_workspace_bytes(hs, ws, channels, code_bits):

@@ -405,14 +405,27 @@ def _forward_generic(self, net, states, params, mask_params, pdf, entropy, selec
     out = torch.clamp(out, 0.0, 5.0)
   overexposure = F.overexposure_penalty(out)
   new_states, penalty = _new_states_and_penalty(cfg, states, filter_one_hot, entropy, overexposure, progress, k)
+  packed = [f.pack(p) for f, p in zip(self.filters, params)]
+  # what a fused replay of this step needs (evaluate.fused_curves_chain): the selected filter's C-ABI id and the
+  # one-hot gather of its packed parameters, zero-padded to the wide row of expo_chain_fused_curves_fwd_ragged
+  width = F._cabi.EXPO_MAX_PARAMS_CURVES
+  with torch.no_grad():  # (a record for replays, not a path of the gradient)
+    params48 = net.new_zeros((net.shape[0], width), dtype=torch.float32)
+    for j, pj in enumerate(packed):
+      pj = pj.float()
+      params48 = params48 + torch.nn.functional.pad(pj, (0, width - pj.shape[1])) * filter_one_hot[:, j:j + 1].float()
+  abi_ids = torch.where(selected_filter_id >= 0, self.abi_filter_ids[selected_filter_id.clamp_min(0).long()],
+                        torch.full_like(selected_filter_id, -1))
   debug_info = {
       'state': states,
       'selected_filter_id': selected_filter_id[0],
       'filter_debug_info': [{'filter_parameters': p[0]} for p in params],
       'pdf': pdf[0],
       'selected_filter_ids': selected_filter_id,
+      'abi_filter_ids': abi_ids,
       'pdf_batch': pdf,
-      'packed_params': [f.pack(p) for f, p in zip(self.filters, params)],
+      'packed_params': packed,
+      'params48': params48,
   }
   if high_res is None:
     return (out, new_states, surrogate, penalty), debug_info, None

@@ -1,12 +1,14 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Fifteen translation units; extra arguments go to every compile step.
+# Fifteen translation units plus chain_fused_curves.hip, the sixteenth; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
 #   chain_fused.hip      the VALU-bound fused inference kernel (-fno-slp-vectorize -fno-honor-nans, see the file)
 #   chain_fused_codes.hip  the fused inference pass reading the files' integer codes (exactly chain_fused.hip's flags:
 #                        it includes that file for the step loop and the stores and must reproduce its outputs bit for bit)
+#   chain_fused_curves.hip  the fused inference pass for any cfg.curve_steps (exactly chain_fused.hip's flags: it
+#                        includes that file and must reproduce its bits for every step that is no curve)
 #   chain_fused_bwd.hip  the one-pass backward of a fixed sequence (-fno-slp-vectorize: the packed-fp32 pairs cost it
 #                        ~100 VGPRs)
 #   nn_ops.hip           the convnets' activation and glue
@@ -62,6 +64,8 @@ p13=$!
 p14=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/codes_lut.hip" -o "$TMP/codes_lut.o" &
 p15=$!
+"$HIPCC" "${FLAGS[@]}" -fno-slp-vectorize -fno-honor-nans "$@" -c "$HERE/chain_fused_curves.hip" -o "$TMP/chain_fused_curves.o" &
+p16=$!
 wait $p1
 wait $p2
 wait $p3
@@ -77,5 +81,6 @@ wait $p12
 wait $p13
 wait $p14
 wait $p15
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" -o "$OUT"
+wait $p16
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -1,0 +1,311 @@
+// chain_fused_curves.hip -- the fused ragged inference pass for ANY cfg.curve_steps L in [1, 16]
+// (expo_chain_fused_curves_fwd_ragged).  expo_chain_fused_fwd_ragged_taps with two other curve steps:
+// Tone (id 4) and Color (id 7) evaluate
+//   y = (L/S) sum_i clip(x - i/L, 0, 1/L) k_i,  S = sum_i k_i + 1e-30
+// for a runtime, wave-uniform L instead of the compile-time 8 of filter_math.h, so a parameter row is
+// EXPO_MAX_PARAMS_CURVES = 3 * 16 floats wide (Tone: k_0..k_{L-1}; Color: channel * L + knot).  Every other step is
+// chain_step's body of chain_fused.hip.
+//
+// A unit of its own, compiled with exactly chain_fused.hip's flags (csrc/build.sh): it includes that file for
+// chain_step, TapSink, the ragged tables and the stores, which it uses untouched, and instantiates none of its kernels
+// (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), so the kernels of chain_fused.hip keep their code and registers.
+//   parameters  chain_fused_run keeps two sets of 24 parameters in SGPRs; two sets of 48 do not fit.  The filters that
+//               are no curve read at most three scalars, so only a row's first three entries (and the id) are fetched
+//               one step ahead through scalar loads; a curve step's knots arrive in a lane-mirrored vector load
+//               (lane l <-> entry l, requested one step ahead as well) and never touch an SGPR.
+//   table       per curve and segment j the line y = a x^ + b of curve_lut_build (kernel_common.h), with L + 1 entries
+//               per curve (entry L repeats L - 1: x^ == 1 needs no index clamp): at most 3 * 17 float2 per wave in LDS,
+//               built once per wave and curve step -- a segmented cross-lane scan (four shuffles) gives the prefix
+//               sums -- for the 24 values a lane maps through it: clamp, mul, cvt, address, ds_read_b64, fma per value,
+//               whatever L is.  The segment is j = min(int(L x^), L - 1), as curve_generic.hip's.
+#define EXPO_CHAIN_FUSED_TEMPLATES_ONLY
+#include "chain_fused.hip"
+
+namespace expo {
+
+namespace {
+
+constexpr int kCurvesMaxL = EXPO_CURVE_MAX_STEPS;
+constexpr int kCurvesTabEntries = 3 * (kCurvesMaxL + 1) + 1;  // 51, padded to an even count
+static_assert(EXPO_MAX_PARAMS_CURVES == 3 * kCurvesMaxL && EXPO_MAX_PARAMS_CURVES <= 64,
+              "a row is three curves of kCurvesMaxL knots, one lane per entry");
+
+// curve_lut_build for a runtime L: lane l < NC * L holds k[l] in klane (other lanes: anything -- masked to 0 here, an
+// entry its filter does not use never enters arithmetic).  All 64 lanes of the wave must be active.
+template <int NC>
+__device__ __forceinline__ void curves_lut_build(float klane, int L, float2_lut* tab) {
+  const int lane = threadIdx.x & 63;
+  const int c = (lane >= L ? 1 : 0) + (lane >= 2 * L ? 1 : 0);  // the curve of this lane, j its segment
+  const int j = lane - c * L;
+  const bool mine = lane < NC * L;
+  const float k = mine ? klane : 0.0f;
+  float incl = k;  // inclusive scan inside each run of L lanes
+#pragma unroll
+  for (int d = 1; d < kCurvesMaxL; d <<= 1) {
+    const float t = __shfl_up(incl, d);
+    if (j >= d) incl += t;
+  }
+  const float inv_s = 1.0f / (__shfl(incl, c * L + L - 1) + 1e-30f);
+  if (mine) {
+    float2_lut e;
+    e.x = float(L) * inv_s * k;
+    e.y = inv_s * ((incl - k) - float(j) * k);
+    const int slot = c * (L + 1) + j;
+    tab[slot] = e;
+    if (j == L - 1) tab[slot + 1] = e;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int NC, int NPIX>
+__device__ __forceinline__ void curves_lut_map(const float* in, float* out, int L, const float2_lut* tab) {
+  const float lf = float(L);
+#pragma unroll
+  for (int k = 0; k < NPIX; ++k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float xc = clamp01x(in[3 * k + c], 0.0f, 1.0f);
+      const int seg = int(xc * lf);  // 0..L; entry L == entry L-1
+      const float2_lut e = tab[(NC == 1 ? 0 : c * (L + 1)) + seg];
+      out[3 * k + c] = fmaf(xc, e.x, e.y);
+    }
+  }
+}
+
+// chain_fused_run for rows of EXPO_MAX_PARAMS_CURVES: prn[steps][48], L the curve steps (uniform), `tab` this wave's
+// kCurvesTabEntries of LDS, `plane` the row entry this lane mirrors.  The loop, the two alternating pixel arrays, the
+// fetch one step ahead and the identity half-trip are chain_fused_run's; see there.
+template <typename T, class Tap = NoTap>
+__device__ inline void chain_fused_curves_run(const int32_t* idn, const float* prn, int steps, int L, float2_lut* tab,
+                                              int plane, float* v, const Tap& tap = Tap()) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  auto apply = [&](int id, const float* prm, float klane, const float* in, float* out) {
+    if (id == 4) {
+      curves_lut_build<1>(klane, L, tab);
+      curves_lut_map<1, PPL>(in, out, L, tab);
+      __builtin_amdgcn_wave_barrier();  // the next curve step of this wave rewrites the table
+    } else if (id == 7) {
+      curves_lut_build<3>(klane, L, tab);
+      curves_lut_map<3, PPL>(in, out, L, tab);
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      chain_step<T>(id, prm, klane, tab, in, out);  // (its own cases 4 and 7 are never reached)
+    }
+  };
+  float pa[3], pb[3];
+  float ka = 0.f, kb = 0.f;
+  int ia = 0, ib = 0;
+  auto fetch = [&](int st, float* p, float& kl, int& id) {
+    const bool live = st < steps;
+    const int sn = live ? st : steps - 1;  // (past the end: any valid row)
+    id = live ? idn[sn] : 0;
+    kl = prn[sn * EXPO_MAX_PARAMS_CURVES + plane];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) p[j] = prn[sn * EXPO_MAX_PARAMS_CURVES + j];
+    if (!live) p[0] = 0.0f;
+  };
+  if (steps <= 0) return;
+  float a[PPL * 3], w[PPL * 3];  // (locals, copied in and out: see chain_fused_run)
+#pragma unroll
+  for (int j = 0; j < PPL * 3; ++j) a[j] = v[j];
+  fetch(0, pa, ka, ia);
+#pragma unroll 1
+  for (int st = 0; st < steps; st += 2) {
+    fetch(st + 1, pb, kb, ib);
+    apply(ia, pa, ka, a, w);
+    tap(st, w);
+    fetch(st + 2, pa, ka, ia);
+    apply(ib, pb, kb, w, a);
+    tap(st + 1, a);  // (st + 1 == steps: the identity half-trip, never a tap)
+  }
+#pragma unroll
+  for (int j = 0; j < PPL * 3; ++j) v[j] = a[j];
+}
+
+// chain_fused_image (Sink = NoSink: stream_groups stores y) / chain_fused_image_taps (yi may be NULL) with the step
+// loop above
+template <typename T, bool VEC, class IO, class Sink>
+__device__ __forceinline__ void chain_fused_curves_image(const int32_t* idn, const float* prn, int steps, int L,
+                                                         const T* xi, T* yi, int hw, int groups, int first_gw,
+                                                         int stride, float2_lut* tab, const Sink& sink) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  constexpr bool kTaps = !std::is_same<Sink, NoSink>::value;
+  const int lane = threadIdx.x & 63;
+  const int plane = lane < EXPO_MAX_PARAMS_CURVES ? lane : EXPO_MAX_PARAMS_CURVES - 1;
+  auto run = [&](float* v, int gw) {
+    if constexpr (kTaps)
+      chain_fused_curves_run<T>(idn, prn, steps, L, tab, plane, v, [&](int k, const float* o) { sink(k, gw, lane, o); });
+    else
+      chain_fused_curves_run<T>(idn, prn, steps, L, tab, plane, v);
+  };
+  if constexpr (VEC) {
+    const T* const ins[1] = {xi};
+    if constexpr (kTaps) {
+#if EXPO_FP16_OVFL
+      // the fp16 stores (y and storage taps) saturate as in stream_groups, which sets this only when it stores itself
+      if constexpr (sizeof(T) == 2) __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);
+#endif
+      const __amdgpu_buffer_rsrc_t ry = make_image_rsrc(yi, hw);
+      stream_groups<T, 1, false, true, IO>(ins, nullptr, hw, first_gw, stride, [&](float (&v)[1][PPL * 3], int g) {
+        const int gw = g - lane;
+        run(v[0], gw);
+        if (yi) store_raw<IO::kStore>(ry, chunk_byte_offset<T>(gw, lane), pack<T>(v[0]));
+      });
+    } else {
+      stream_groups<T, 1, true, false, IO>(ins, yi, hw, first_gw, stride,
+                                           [&](float (&v)[1][PPL * 3], int g) { run(v[0], g - lane); });
+    }
+  } else {
+    for (int g0 = first_gw; g0 < groups; g0 += stride) {  // wave-uniform trip count: the table builds need every lane
+      const int g = g0 + lane;
+      float v[PPL * 3];
+      load_slow<T>(xi, g, hw, v);
+      run(v, g0);
+      if (!kTaps || yi) store_slow<T>(yi, g, hw, v);
+    }
+  }
+}
+
+// FMT kTapNone: the table of chain_fused_fwd_ragged_kernel, otherwise the one with a tap buffer per image
+template <typename T, int FMT>
+using CurvesTable = typename std::conditional<FMT == kTapNone, RaggedTable<T>, RaggedTapTable<T>>::type;
+
+template <typename T, class IO, bool ANY_SLOW, int FMT>
+__global__ __launch_bounds__(kThreads) void chain_fused_curves_ragged_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ params, int steps, int L, uint64_t tap_mask,
+    const CurvesTable<T, FMT> tt) {
+  __shared__ float2_lut curve_tab[kWaves][kCurvesTabEntries];
+  __shared__ __attribute__((aligned(4))) uint8_t tap_stage[kWaves][TapStage<T, FMT>::kBytes];
+  const RaggedTable<T>& tab = [&]() -> const RaggedTable<T>& {
+    if constexpr (FMT == kTapNone) return tt;
+    else return tt.t;
+  }();
+  const int b = blockIdx.x;
+  int lo = 0, hi = tab.n - 1;  // the last image whose first block is <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab.first[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int i = __builtin_amdgcn_readfirstlane(lo);
+  constexpr int PPL = PixTraits<T>::PPL;
+  const int hw = tab.hw[i];
+  const int groups = (hw + PPL - 1) / PPL;
+  const int first_gw = (b - tab.first[i]) * kThreads + (threadIdx.x & ~63);
+  const int stride = (tab.first[i + 1] - tab.first[i]) * kThreads;
+  const int32_t* idn = ids + size_t(i) * steps;
+  const float* prn = params + size_t(i) * steps * EXPO_MAX_PARAMS_CURVES;
+  float2_lut* const lut = curve_tab[threadIdx.x >> 6];
+  auto image = [&](auto vec) {
+    constexpr bool VEC = decltype(vec)::value;
+    if constexpr (FMT == kTapNone) {
+      chain_fused_curves_image<T, VEC, IO>(idn, prn, steps, L, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut,
+                                           NoSink());
+    } else {
+      using Sink = TapSink<T, VEC, IO, FMT>;
+      const Sink sink{tt.taps[i], size_t(hw) * 3 * Sink::ES, tap_mask, hw, tap_stage[threadIdx.x >> 6]};
+      chain_fused_curves_image<T, VEC, IO>(idn, prn, steps, L, tab.x[i], tab.y[i], hw, groups, first_gw, stride, lut,
+                                           sink);
+    }
+  };
+  if (!ANY_SLOW || ((tab.vec >> i) & 1)) image(std::true_type());
+  else image(std::false_type());
+}
+
+// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output.
+// The launches, their split and the vector decision are chain_fused_fwd_ragged_t's / chain_fused_fwd_ragged_taps_t's.
+template <typename T, int FMT>
+int chain_fused_curves_ragged_t(const int32_t* ids, const float* params, int steps, int L, const void* const* xs,
+                                void* const* ys, const int* hs, const int* ws, int n, uint64_t tap_mask,
+                                void* const* taps, hipStream_t s) {
+  constexpr int PPL = PixTraits<T>::PPL;
+  long bytes = 0;  // cache policy from the bytes of the whole call
+  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
+  const bool stream = bytes >= stream_min_bytes();
+  for (int base = 0; base < n; base += kRaggedMaxImages) {
+    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
+    CurvesTable<T, FMT> tt = {};
+    RaggedTable<T>& tab = [&]() -> RaggedTable<T>& {
+      if constexpr (FMT == kTapNone) return tt;
+      else return tt.t;
+    }();
+    tab.n = m;
+    bool any_slow = false;
+    long blocks = 0;
+    for (int j = 0; j < m; ++j) {
+      const int i = base + j, hw = hs[i] * ws[i];
+      tab.x[j] = static_cast<const T*>(xs[i]);
+      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+      uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]);
+      if constexpr (FMT != kTapNone) {
+        tt.taps[j] = static_cast<char*>(taps[i]);
+        if (tap_vector_store<T, FMT>()) a |= reinterpret_cast<uintptr_t>(taps[i]);
+      }
+      tab.hw[j] = hw;
+      tab.first[j] = int(blocks);
+      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
+      const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
+      if (vec) tab.vec |= uint64_t(1) << j;
+      any_slow = any_slow || !vec;
+    }
+    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+    tab.first[m] = int(blocks);
+    const int32_t* idb = ids + size_t(base) * steps;
+    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS_CURVES;
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
+    if (stream && any_slow)
+      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoStream, true, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
+    else if (stream)
+      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoStream, false, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
+    else if (any_slow)
+      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoCached, true, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
+    else
+      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoCached, false, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
+    HIP_TRY(hipGetLastError(), "chain_fused_curves_fwd_ragged launch");
+  }
+  return EXPO_OK;
+}
+
+// kernel arguments: ids, params, steps, L, tap_mask, the table
+static_assert(sizeof(RaggedTapTable<half_t>) + 40 <= 4096, "the ragged tap table must fit the 4 KB kernarg block");
+
+}  // namespace
+
+}  // namespace expo
+
+using namespace expo;
+
+extern "C" {
+
+int expo_chain_fused_curves_fwd_ragged(const int32_t* filter_ids, const float* params, int steps, int curve_steps,
+                                       const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
+                                       int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
+  // everything is checked before the first launch is enqueued
+  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
+  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
+  if (curve_steps < 1 || curve_steps > kCurvesMaxL)
+    return fail(EXPO_E_BADARG, "curve_steps must be in [1, EXPO_CURVE_MAX_STEPS]");
+  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
+  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
+  if (n == 0) return EXPO_OK;
+  if (!xs || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
+    return fail(EXPO_E_BADARG, "null pointer");
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
+    if (!xs[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
+    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int L = curve_steps;
+#define EXPO_CURVES(T, FMT) \
+  chain_fused_curves_ragged_t<T, FMT>(filter_ids, params, steps, L, xs, ys, hs, ws, n, tap_mask, taps, s)
+  const bool f16 = dtype == EXPO_F16;
+  if (!tap_mask) return f16 ? EXPO_CURVES(half_t, kTapNone) : EXPO_CURVES(float, kTapNone);
+  if (tap_format == EXPO_TAP_U8) return f16 ? EXPO_CURVES(half_t, EXPO_TAP_U8) : EXPO_CURVES(float, EXPO_TAP_U8);
+  if (tap_format == EXPO_TAP_U16) return f16 ? EXPO_CURVES(half_t, EXPO_TAP_U16) : EXPO_CURVES(float, EXPO_TAP_U16);
+  return f16 ? EXPO_CURVES(half_t, EXPO_TAP_STORAGE) : EXPO_CURVES(float, EXPO_TAP_STORAGE);
+#undef EXPO_CURVES
+}
+
+}  // extern "C"

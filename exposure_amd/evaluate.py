@@ -149,6 +149,35 @@ def fused_masked_chain_ragged(images, filter_ids, params24, mask6, cfg, tap_mask
   return ys, taps
 
 
+def fused_curves_chain(high_res, filter_ids, params48, curve_steps, tap_mask=0, tap_dtype=None, out=True):
+  """``fused_chain_taps`` for any ``cfg.curve_steps`` (``expo_chain_fused_curves_fwd_ragged``): params48 (N, steps, 48)
+  are the wide rows the agent recorded (``debug_info['params48']``), ``curve_steps`` the L the curve rows are packed
+  for.  The dense tensor goes in as N views of one ragged call; the taps come back as a (T, N, H, W, 3) view of an
+  image-major buffer."""
+  from . import _cabi
+  x = high_res.contiguous()
+  n, t = x.shape[0], bin(tap_mask).count('1')
+  y = torch.empty_like(x) if out else None
+  taps = torch.empty((n, t) + tuple(x.shape[1:]), dtype=tap_dtype or x.dtype, device=x.device)
+  _cabi.chain_fused_curves_fwd_ragged(filter_ids.contiguous().to(torch.int32), params48.contiguous().float(),
+                                      int(curve_steps), list(x.unbind(0)), list(y.unbind(0)) if out else None, tap_mask,
+                                      list(taps.unbind(0)) if t else None)
+  return y, taps.transpose(0, 1)
+
+
+def fused_curves_chain_ragged(images, filter_ids, params48, curve_steps, tap_mask=0, tap_dtype=None, out=True):
+  """``fused_chain_ragged_taps`` for any ``cfg.curve_steps``: (outs or None, per image a (T, H_i, W_i, 3) tensor of
+  ``tap_dtype``), one ragged launch per 64 images."""
+  from . import _cabi
+  xs = [im.contiguous() for im in images]
+  ys = [torch.empty_like(x) for x in xs] if out else None
+  t = bin(tap_mask).count('1')
+  taps = [torch.empty((t,) + tuple(x.shape[-3:]), dtype=tap_dtype or x.dtype, device=x.device) for x in xs]
+  _cabi.chain_fused_curves_fwd_ragged(filter_ids.contiguous().to(torch.int32), params48.contiguous().float(),
+                                      int(curve_steps), xs, ys, tap_mask, taps if t else None)
+  return ys, taps
+
+
 def encode_u8(img):
   """``save_png``'s 8-bit encoding on the device: saturate(round_half_even(float(img) * 255))."""
   return torch.round(img.float() * 255.0).clamp_(0, 255).to(torch.uint8)
@@ -164,6 +193,7 @@ def encode_u16(img):
 INTERMEDIATES = (None, 'u8', 'u16', 'storage')
 PICTURES = (False, True, 'u8', 'u16')
 MASKS = ('stepwise', 'fused')
+CURVES = ('stepwise', 'fused')
 _CODE_DTYPES = {'u8': torch.uint8, 'u16': torch.uint16}
 _ENCODERS = {'u8': encode_u8, 'u16': encode_u16}
 
@@ -187,12 +217,13 @@ def _intermediate_mask(stops):
   return sum(1 << i for i, stopped in enumerate(stops) if not stopped)
 
 
-def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, keep_hi=False, mask6=None):
+def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, keep_hi=False, mask6=None, params48=None):
   """The agent loop of ``retouch`` on the (N, 64, 64, 3) proxies: ``steps`` steps (or until every image stopped), the
   full-resolution tensor ``hi`` filtered at every step when given (the reference's schedule).  Returns low, states,
   hi, and per step the selected ids, the C-ABI ids, the (N, 24) parameter rows, whether every image was stopped after
   it and (``keep_hi``) the full-resolution tensor after it.  ``mask6``: a list that receives every step's (N, 6)
-  squashed mask rows when the agent reports them (``cfg.masking``)."""
+  squashed mask rows when the agent reports them (``cfg.masking``).  ``params48``: a list that receives every step's
+  (N, 48) wide parameter rows of a ``generic`` agent, whose C-ABI ids are then the ones it reports."""
   cfg = agent.cfg
   n, dev = low.shape[0], low.device
   states = torch.zeros((n, cfg.num_state_dim), dtype=torch.float32, device=dev)  # get_initial_states
@@ -205,7 +236,11 @@ def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, ke
       (low, states, hi), dbg, _ = agent((low, z, states), is_train=0, progress=0.0, high_res=hi,
                                         dropout_masks=masks)
     if generic:  # no (N, 24) parameter rows exist for this configuration: record the ids only
-      abi_ids.append(agent.abi_filter_ids[dbg['selected_filter_ids'].clamp_min(0).long()])
+      if params48 is not None:  # (and the rows of the fused pass for any curve_steps)
+        abi_ids.append(dbg['abi_filter_ids'])
+        params48.append(dbg['params48'])
+      else:
+        abi_ids.append(agent.abi_filter_ids[dbg['selected_filter_ids'].clamp_min(0).long()])
       params.append(torch.zeros((n, 24), dtype=torch.float32, device=dev))
     else:
       abi_ids.append(dbg['abi_filter_ids'])
@@ -221,12 +256,14 @@ def _agent_steps(agent, low, z, steps, dropout_masks, hi=None, generic=False, ke
   return low, states, hi, trace, abi_ids, params, stops, his
 
 
-def _trace_result(out, low, states, trace, abi_ids, params, return_trace, mask6=()):
+def _trace_result(out, low, states, trace, abi_ids, params, return_trace, mask6=(), params48=()):
   if return_trace == 'full':  # the per-step operations (what net.py:825-877 pickles as decisions / operations)
     ops = dict(selected=torch.stack(trace, dim=1), abi_filter_ids=torch.stack(abi_ids, dim=1),
                params24=torch.stack(params, dim=1))
     if mask6:  # cfg.masking: the (N, S, 6) squashed mask rows of the selected filters
       ops['mask6'] = torch.stack(mask6, dim=1)
+    if params48:  # curves='fused': the (N, S, 48) rows fused_curves_chain replays (params24 is all zero then)
+      ops['params48'] = torch.stack(params48, dim=1)
     return out, low, states, ops
   if return_trace:
     return out, low, states, torch.stack(trace, dim=1)
@@ -235,7 +272,7 @@ def _trace_result(out, low, states, trace, abi_ids, params, return_trace, mask6=
 
 @torch.no_grad()
 def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trace=False, fused=True,
-            intermediates=None, proxy='torch', picture=False, masks='stepwise'):
+            intermediates=None, proxy='torch', picture=False, masks='stepwise', curves='stepwise'):
   """Run the 5-step retouching loop.  ``high_res``: NHWC device tensor (fp16/fp32), linear RGB.
   Returns (retouched_high_res, retouched_low_res, states[, trace of selected filter ids][, intermediates]).
 
@@ -261,7 +298,13 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   ``'fused'``: the spatial mask of a step needs the pixel's position, the running value's luminance and six numbers the
   agent regresses on the proxy, so the fused pass takes it too (``fused_masked_chain``): the agent runs on the proxies
   only, and intermediates, picture and trace come as on the unmasked fused path.  fp32 between steps instead of one
-  storage rounding per step.  ``fused=False`` wins over it."""
+  storage rounding per step.  ``fused=False`` wins over it.
+
+  ``curves`` matters only for an agent with a generic curve filter (``cfg.curve_steps != 8``).  ``'stepwise'`` (default):
+  the reference's schedule on the generic kernels, as ``fused=False``.  ``'fused'``: the agent runs on the proxies only,
+  recording each step's C-ABI id and wide parameter row (``debug_info['params48']``), and ``fused_curves_chain`` applies
+  them in one pass; intermediates, picture and trace come as on the 8-step fused path, and a ``'full'`` trace also
+  carries ``params48`` (N, S, 48).  ``fused=False`` wins over it, and ``cfg.masking`` keeps the stepwise schedule."""
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
@@ -269,11 +312,14 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
     raise ValueError('proxy must be one of %s' % (PROXIES,))
   if masks not in MASKS:
     raise ValueError('masks must be one of %s' % (MASKS,))
+  if curves not in CURVES:
+    raise ValueError('curves must be one of %s' % (CURVES,))
   kind = _picture_kind(picture, intermediates)
   if cfg.masking and masks != 'fused':
     fused = False  # the reference's schedule: every step filters the full-resolution tensor
   generic = any(f.uses_generic_kernels() for f in agent.filters)
-  if generic:
+  fused_curves = generic and fused and curves == 'fused' and not cfg.masking
+  if generic and not fused_curves:
     fused = False  # cfg.curve_steps != 8: the one-pass kernel is instantiated for 8-step curves (reference schedule instead)
   steps = steps or cfg.test_steps
   n = high_res.shape[0]
@@ -285,30 +331,34 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
   if z is None:
     z = torch.rand((n, cfg.z_dim), device=dev)
   hi = high_res.contiguous()
-  mask6 = []
+  mask6, wide = [], []
   low, states, stepped, trace, abi_ids, params, stops, his = _agent_steps(
       agent, low, z, steps, dropout_masks, hi=None if fused else hi, generic=generic,
-      keep_hi=bool(intermediates) and not fused, mask6=mask6)
+      keep_hi=bool(intermediates) and not fused, mask6=mask6, params48=wide if fused_curves else None)
+  rows = wide if fused_curves else params  # the parameter rows of the fused pass
   mask = _intermediate_mask(stops)
   inter = pic = None
   last = 1 << (len(stops) - 1)  # the last executed step: its u8 / u16 tap is the picture of the output
   if fused and cfg.masking:  # the same pass with the spatial masks
     def chain_taps(x, ids, prm, tap_mask, tap_dtype):
       return fused_masked_chain(x, ids, prm, torch.stack(mask6, dim=1), cfg, tap_mask, tap_dtype)
+  elif fused_curves:  # the same pass for this cfg.curve_steps
+    def chain_taps(x, ids, prm, tap_mask, tap_dtype):
+      return fused_curves_chain(x, ids, prm, cfg.curve_steps, tap_mask, tap_dtype)
   else:
     chain_taps = fused_chain_taps
   if fused and kind and intermediates != 'storage':
     # one pass: the output, the picture and (u8 / u16) the intermediates, which are the taps before the last
-    hi, taps = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1),
+    hi, taps = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(rows, dim=1),
                           (mask if intermediates else 0) | last, _CODE_DTYPES[kind])
     pic = taps[-1]
     if intermediates:
       inter = taps if mask & last else taps[:-1]
   elif fused and intermediates:
-    hi, inter = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), mask,
+    hi, inter = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(rows, dim=1), mask,
                            _CODE_DTYPES.get(intermediates, hi.dtype))
-  elif fused and cfg.masking:
-    hi, _ = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1), 0, None)
+  elif fused and (cfg.masking or fused_curves):
+    hi, _ = chain_taps(hi, torch.stack(abi_ids, dim=1), torch.stack(rows, dim=1), 0, None)
   elif fused:
     hi = fused_chain(hi, torch.stack(abi_ids, dim=1), torch.stack(params, dim=1))
   else:
@@ -320,13 +370,13 @@ def retouch(agent, high_res, steps=None, z=None, dropout_masks=None, return_trac
         inter = _ENCODERS[intermediates](inter)
   if kind and pic is None:
     pic = _ENCODERS[kind](hi)
-  res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace, mask6)
+  res = _trace_result(hi, low, states, trace, abi_ids, params, return_trace, mask6, wide)
   return res + ((inter,) if intermediates else ()) + ((pic,) if kind else ())
 
 
 @torch.no_grad()
 def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_trace=False, intermediates=None,
-                  proxy='torch', picture=False, masks='stepwise'):
+                  proxy='torch', picture=False, masks='stepwise', curves='stepwise'):
   """``retouch`` over a list of images of ANY sizes at once (the batching ``evaluate.py:18`` asks for, without its
   same-resolution restriction).  ``images``: N device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3), one dtype and device.
   One 64x64 proxy per image (``make_low_res``) is stacked, the agent runs once on the (N, 64, 64, 3) stack, and the
@@ -346,7 +396,9 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
   (``'u16'``: uint16 pictures).
 
   ``masks='fused'`` with ``cfg.masking`` keeps the batch together as without masks: one agent call on the stacked
-  proxies, then ``fused_masked_chain_ragged`` (see ``retouch``); the default ``'stepwise'`` runs every image alone."""
+  proxies, then ``fused_masked_chain_ragged`` (see ``retouch``); the default ``'stepwise'`` runs every image alone.
+  ``curves='fused'`` does the same for an agent with generic curve filters (``cfg.curve_steps != 8``, masking off):
+  one agent call, then ``fused_curves_chain_ragged``; the default ``'stepwise'`` runs every image alone."""
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
@@ -354,6 +406,8 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     raise ValueError('proxy must be one of %s' % (PROXIES,))
   if masks not in MASKS:
     raise ValueError('masks must be one of %s' % (MASKS,))
+  if curves not in CURVES:
+    raise ValueError('curves must be one of %s' % (CURVES,))
   kind = _picture_kind(picture, intermediates)
   images = list(images)
   n = len(images)
@@ -369,12 +423,13 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     z = torch.rand((n, cfg.z_dim), device=dev)
   hi4 = [im if im.dim() == 4 else im[None] for im in images]
   generic = any(f.uses_generic_kernels() for f in agent.filters)
-  if (cfg.masking and masks != 'fused') or generic:  # per image, the schedule retouch picks for it
+  fused_curves = generic and curves == 'fused' and not cfg.masking
+  if (cfg.masking and masks != 'fused') or (generic and not fused_curves):  # per image, the schedule retouch picks for it
     rows = []
     for i, im in enumerate(hi4):
       drop = None if dropout_masks is None else [tuple(m[i:i + 1] for m in step) for step in dropout_masks]
       rows.append(retouch(agent, im, steps=steps, z=z[i:i + 1], dropout_masks=drop, return_trace=return_trace or True,
-                          intermediates=intermediates, proxy=proxy, picture=picture, masks=masks))
+                          intermediates=intermediates, proxy=proxy, picture=picture, masks=masks, curves=curves))
     outs = [r[0].reshape(im.shape) for r, im in zip(rows, images)]
     low, states = torch.cat([r[1] for r in rows]), torch.cat([r[2] for r in rows])
     extra = ([r[4][:, 0] for r in rows],) if intermediates else ()
@@ -389,32 +444,37 @@ def retouch_batch(agent, images, steps=None, z=None, dropout_masks=None, return_
     low = make_low_res_batch(images, cfg.source_img_size)
   else:
     low = torch.cat([make_low_res(im, cfg.source_img_size) for im in hi4])
-  mask6 = []
-  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks, mask6=mask6)
-  ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
+  mask6, wide = [], []
+  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(
+      agent, low, z, steps, dropout_masks, generic=generic, mask6=mask6, params48=wide if fused_curves else None)
+  ids, prm = torch.stack(abi_ids, dim=1), torch.stack(wide if fused_curves else params, dim=1)
   if cfg.masking:  # the same launches with the spatial masks
     def ragged_taps(xs, ids, prm, tap_mask, tap_dtype):
       return fused_masked_chain_ragged(xs, ids, prm, torch.stack(mask6, dim=1), cfg, tap_mask, tap_dtype)
+  elif fused_curves:  # the same launches for this cfg.curve_steps
+    def ragged_taps(xs, ids, prm, tap_mask, tap_dtype):
+      return fused_curves_chain_ragged(xs, ids, prm, cfg.curve_steps, tap_mask, tap_dtype)
   else:
     ragged_taps = fused_chain_ragged_taps
   if kind and intermediates != 'storage':
     # one ragged launch: the outputs, the pictures and (u8 / u16) the intermediates, which are the taps before the last
     mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
     outs, taps = ragged_taps(images, ids, prm, (mask if intermediates else 0) | last, _CODE_DTYPES[kind])
-    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
+    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6, wide)
     if intermediates:
       res += ([t if mask & last else t[:-1] for t in taps],)
     return res + ([t[-1] for t in taps],)
   if kind:  # storage intermediates: the taps of a launch have one format, so the pictures are encoded from the outputs
     outs, inter = ragged_taps(images, ids, prm, _intermediate_mask(stops), images[0].dtype)
-    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
+    res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6, wide)
     return res + (inter, [_ENCODERS[kind](o.reshape(o.shape[-3:])) for o in outs])
   if not intermediates:
-    outs = ragged_taps(images, ids, prm, 0, None)[0] if cfg.masking else fused_chain_ragged(images, ids, prm)
-    return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6)
+    outs = ragged_taps(images, ids, prm, 0, None)[0] if cfg.masking or fused_curves else \
+        fused_chain_ragged(images, ids, prm)
+    return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6, wide)
   outs, inter = ragged_taps(images, ids, prm, _intermediate_mask(stops),
                             _CODE_DTYPES.get(intermediates, images[0].dtype))
-  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6) + (inter,)
+  return _trace_result(outs, low, states, trace, abi_ids, params, return_trace, mask6, wide) + (inter,)
 
 
 def load_image(path):
@@ -800,6 +860,14 @@ def main(argv=None):
   ap.add_argument('--fused-masks', action='store_true',
                   help='with --masking: apply the masked steps in the one fused pass (fp32 between steps, taps, --batch '
                   'in one ragged launch) instead of step by step.  --stepwise wins over it')
+  ap.add_argument('--curve-steps', type=int, default=None, metavar='L',
+                  help='cfg.curve_steps, 1..16 (default 8): the knots of the Tone and Color curves, which sets the '
+                  "shapes of their heads -- weights trained with another L do not load.  L != 8 runs the reference's "
+                  'schedule on the generic kernels unless --fused-curves is given')
+  ap.add_argument('--fused-curves', action='store_true',
+                  help='with --curve-steps L != 8: apply the steps in the one fused pass for any L (fp32 between steps, '
+                  'taps, --batch in one ragged launch) instead of step by step.  Not with --stepwise; --masking keeps '
+                  'the stepwise schedule; no effect with 8-step curves')
   ap.add_argument('--batch', type=int, default=1, metavar='N',
                   help='retouch up to N images at once, of any sizes, grouped in argument order (retouch_batch: the '
                   'agent runs on the stacked proxies, one ragged launch applies the filters).  z and the dropout '
@@ -851,6 +919,12 @@ def main(argv=None):
   cfg = make_cfg(filters=flt)
   if args.masking:
     cfg.masking = True
+  if args.curve_steps is not None:
+    if not 1 <= args.curve_steps <= 16:
+      ap.error('--curve-steps must be in 1..16')
+    cfg.curve_steps = args.curve_steps
+  if args.fused_curves and args.stepwise:
+    ap.error('--fused-curves does not go with --stepwise: they are two schedules of the full-resolution pass')
   agent = Agent(cfg).to(dev)
   if args.weights and args.tf_checkpoint:
     ap.error('--weights and --tf-checkpoint are alternatives')
@@ -868,6 +942,8 @@ def main(argv=None):
   if args.score:
     args.device_png = True
   if args.fused_decode:
+    if any(f.uses_generic_kernels() for f in agent.filters):
+      ap.error('--fused-decode needs 8-step curves: there is no pass from codes for --curve-steps %d' % cfg.curve_steps)
     if args.stepwise or args.masking or ((args.show_input or args.show_linear) and not args.device_input_png):
       ap.error('--fused-decode does not go with --stepwise, --masking or --show-input: the pass from codes is the '
                'unmasked fused one, and the tone-mapped picture needs the float input')
@@ -883,6 +959,7 @@ def main(argv=None):
   inter_kind = code if args.step_by_step else None
   picture = 'u16' if args.tiff16 else args.device_png  # the pictures retouch makes on the device
   masks = 'fused' if args.fused_masks else 'stepwise'
+  curves = 'fused' if args.fused_curves else 'stepwise'
   records = []
   pictures = []  # --score: every emitted image's uint8 picture, kept on the device (not the float outputs)
 
@@ -970,7 +1047,7 @@ def main(argv=None):
     for path in args.images:
       (hi,), inps = load_group([path])
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
-                    picture=picture, masks=masks)
+                    picture=picture, masks=masks, curves=curves)
       emit(path, hi, res[0], res[2], res[3], res[4][:, 0] if inter_kind else None,
            res[-1][0] if picture else None, inps[0] if inps else None)
   else:
@@ -978,7 +1055,7 @@ def main(argv=None):
       paths = args.images[b:b + args.batch]
       his, inps = load_group(paths)
       res = retouch_batch(agent, his, return_trace='full', intermediates=inter_kind, proxy=proxy,
-                          picture=picture, masks=masks)
+                          picture=picture, masks=masks, curves=curves)
       emit_batch(paths, his, res, inps)
   if args.score:
     import random

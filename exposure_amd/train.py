@@ -36,6 +36,9 @@ def parse_args(argv=None):
                   help="also write MODEL_DIR/model.ckpt-<iters> in TensorFlow's checkpoint format, variable names and "
                   "layouts as the reference's graph declares them (net.py:380-384)")
   ap.add_argument('--clamp', action='store_true', help='cfg.clamp = True (agent.py:240-241)')
+  ap.add_argument('--curve-steps', type=int, default=None, metavar='L',
+                  help='cfg.curve_steps, 1..16 (default 8): the knots of the Tone and Color curves (L != 8 trains on '
+                  'the generic curve kernels)')
   ap.add_argument('--dtype', default='f32', choices=['f32', 'f16'], help='storage type of the image pool')
   ap.add_argument('--fake-dir', default=None, help='folder of input photos (with --real-dir; default: synthetic data)')
   ap.add_argument('--real-dir', default=None, help='folder of target photos (with --fake-dir)')
@@ -46,6 +49,8 @@ def parse_args(argv=None):
   ap.add_argument('--read-limit', type=int, default=-1, help='read at most this many files of each folder')
   ap.add_argument('--pack-cache', default=None, metavar='DIR', help='keep the built packs under DIR/fake and DIR/real')
   args = ap.parse_args(argv)
+  if args.curve_steps is not None and not 1 <= args.curve_steps <= 16:
+    ap.error('--curve-steps must be in 1..16')
   if (args.fake_dir is None) != (args.real_dir is None):
     ap.error('--fake-dir and --real-dir go together')
   if args.fake_dir is None:
@@ -88,6 +93,8 @@ def main(argv=None):
   torch.manual_seed(args.seed)
   cfg = make_cfg()
   cfg.clamp = bool(args.clamp)
+  if args.curve_steps is not None:
+    cfg.curve_steps = args.curve_steps
   gan = GAN(cfg, device=dev, use_graphs=not args.no_graphs, seed=args.seed)  # (--seed also drives dropout / alpha)
   dt = torch.float32 if args.dtype == 'f32' else torch.float16
   if args.fake_dir is not None:

@@ -59,7 +59,7 @@ extern "C" {
                               expo_patch_stats, expo_stat_hist, expo_chain_fused_masked_fwd_ragged,
                               expo_decode_tables, expo_bilinear_resize_ragged_codes,
                               expo_chain_fused_fwd_ragged_codes, expo_codes_max_ragged,
-                              expo_codes_lut_ragged */
+                              expo_codes_lut_ragged, expo_chain_fused_curves_fwd_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -73,6 +73,7 @@ extern "C" {
 #define EXPO_MAX_PARAMS 24
 #define EXPO_MAX_HEADS 16 /* FC heads one expo_heads_regress_* call serves (cfg.filters has 8) */
 #define EXPO_CURVE_MAX_STEPS 16 /* largest cfg.curve_steps of expo_curve_fwd / _bwd */
+#define EXPO_MAX_PARAMS_CURVES 48 /* a parameter row of expo_chain_fused_curves_fwd_ragged: 3 x EXPO_CURVE_MAX_STEPS */
 
 #define EXPO_FILTER_EXPOSURE 0
 #define EXPO_FILTER_GAMMA 1
@@ -378,6 +379,28 @@ int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* par
  */
 int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* params, const float* mask_params,
                                        int steps, float maximum_sharpness, float minimum_strength,
+                                       const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
+                                       int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
+
+/*
+ * The fused inference pass for any cfg.curve_steps: an added export of ABI 9 (the version is unchanged).  It replaces
+ * the high-resolution loop of net.py:796-823 with the curves of filters.py:264-273, 312-322 for any L, where
+ * expo_chain_fused_fwd_ragged_taps is built for L = 8.
+ *   filter_ids   device int32 [n][steps] in [-1, 8]
+ *   params       device float32 [n][steps][EXPO_MAX_PARAMS_CURVES].  Ids 0, 1, 2, 3, 5, 6, 8 keep their packing at the
+ *                front of the row (at most 3 values); Tone (4) holds k_0 .. k_{L-1}; Color (7) holds channel * L + knot
+ *                (ColorFilter.pack for that L).  Entries a filter does not use never enter arithmetic.
+ *   curve_steps  L in [1, EXPO_CURVE_MAX_STEPS], one value for the call.  Ids 4 and 7 evaluate, per channel value x,
+ *                  y = (L/S) sum_i clip(x - i/L, 0, 1/L) k_i,  S = sum_i k_i + 1e-30
+ *                through the segment form of expo_curve_fwd: x^ = clamp(x, 0, 1), j = min(int(x^ L), L - 1).
+ *                L = 8 is allowed (the curve steps then differ from expo_chain_fused_fwd_ragged_taps in rounding only).
+ * Everything else -- fp32 between steps and one rounding to storage at the end, id -1 -> +0, steps == 0 -> the input's
+ * bits, xs / ys / hs / ws, the launches of up to 64 images, the per-image choice of the dwordx3 path, the cache policy
+ * from the call's total bytes, tap_mask / tap_format / taps, ys NULL with taps, and the validation -- is exactly
+ * expo_chain_fused_fwd_ragged_taps; a sequence without ids 4 and 7 gives that entry point's bits.  curve_steps outside
+ * its range is EXPO_E_BADARG; n == 0 is EXPO_OK.  No backward.
+ */
+int expo_chain_fused_curves_fwd_ragged(const int32_t* filter_ids, const float* params, int steps, int curve_steps,
                                        const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                        int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
 
