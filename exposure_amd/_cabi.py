@@ -148,6 +148,13 @@ SIGNATURES = {
     'expo_curve_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'expo_curve_fwd': (_i, [_vp, _vp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
     'expo_curve_bwd': (_i, [_vp, _vp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'expo_filter_dispatch_curves_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'expo_filter_dispatch_curves_fwd': (_i, [_vp, _vp, _vp, _fp, _i, _fp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'expo_filter_dispatch_curves_bwd': (_i, [_vp, _vp, _vp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'expo_heads_regress_curves_fwd': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, ctypes.POINTER(_f),
+                                           _vp, _fp, _i, _i, _vp]),
+    'expo_heads_regress_curves_bwd': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i,
+                                           ctypes.POINTER(_f), _vp, _fp, _i, _i, _vp]),
 }
 
 _lib = None
@@ -1527,6 +1534,97 @@ def curve_bwd(x, dy, dx, params, dparams, curves, steps, workspace=None):
     _check(lib.expo_curve_bwd(_ptr(x), _ptr(dy), _ptr(dx), _ptr(params), _ptr(dparams), n, h, w, _dtype_code(x),
                               int(curves), int(steps), ctypes.c_void_p(workspace.data_ptr()),
                               ctypes.c_size_t(workspace.numel() * workspace.element_size()), _stream()), 'expo_curve_bwd')
+
+
+def _curve_steps(curve_steps):
+  curve_steps = int(curve_steps)
+  if not 1 <= curve_steps <= EXPO_CURVE_MAX_STEPS:
+    raise ExposureHipError('exposure_amd: curve_steps must be in [1, %d], got %d' % (EXPO_CURVE_MAX_STEPS, curve_steps))
+  return curve_steps
+
+
+def dispatch_curves_workspace_bytes(n, h, w, dtype_code, curve_steps):
+  return int(load().expo_filter_dispatch_curves_workspace_bytes(int(n), int(h), int(w), int(dtype_code), int(curve_steps)))
+
+
+def _ws_curves(x, curve_steps, workspace):
+  """(pointer, size) of the workspace of the dispatch for any cfg.curve_steps: the device's shared pool unless given."""
+  n, h, w, _ = x.shape
+  need = dispatch_curves_workspace_bytes(n, h, w, _dtype_code(x), curve_steps)
+  if workspace is None:
+    workspace = reserve_workspace(x.device, need)
+    _order_shared_workspace(x.device)
+  if not workspace.is_cuda or workspace.device != x.device or workspace.numel() * workspace.element_size() < need:
+    raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' % (need, x.device))
+  return ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel() * workspace.element_size())
+
+
+def dispatch_curves_fwd(ids, x, y, params, curve_steps, penalty=None, workspace=None):
+  """expo_filter_dispatch_curves_fwd: image n through filter ids[n] (-1: y = 0) with params (N, EXPO_MAX_PARAMS_CURVES);
+  ids 4 / 7 are curves of ``curve_steps`` steps.  penalty (N,) float32, optional: the fused over-exposure term."""
+  lib = load()
+  _img(x, 'x'), _img(y, 'y')
+  n, h, w, _ = x.shape
+  assert y.shape == x.shape and y.dtype == x.dtype
+  curve_steps = _curve_steps(curve_steps)
+  _ids(ids, n)
+  _f32(params, 'params', (n, EXPO_MAX_PARAMS_CURVES))
+  if penalty is not None:
+    _f32(penalty, 'penalty', (n,))
+  with torch.cuda.device(x.device):
+    wsp, wsb = _ws_curves(x, curve_steps, workspace)
+    _check(
+        lib.expo_filter_dispatch_curves_fwd(_ptr(ids), _ptr(x), _ptr(y), _ptr(params), curve_steps, _ptr(penalty), n, h, w,
+                                            _dtype_code(x), wsp, wsb, _stream()), 'expo_filter_dispatch_curves_fwd')
+
+
+def dispatch_curves_bwd(ids, x, dy, dx, params, dparams, curve_steps, dpenalty=None, hsv_grad_mode=0, workspace=None):
+  """expo_filter_dispatch_curves_bwd: dx (optional) and dparams (N, EXPO_MAX_PARAMS_CURVES), fully overwritten."""
+  lib = load()
+  _img(x, 'x'), _img(dy, 'dy')
+  n, h, w, _ = x.shape
+  assert dy.shape == x.shape and dy.dtype == x.dtype
+  curve_steps = _curve_steps(curve_steps)
+  _ids(ids, n)
+  if dx is not None:
+    _img(dx, 'dx')
+    assert dx.shape == x.shape and dx.dtype == x.dtype
+  _f32(params, 'params', (n, EXPO_MAX_PARAMS_CURVES))
+  _f32(dparams, 'dparams', (n, EXPO_MAX_PARAMS_CURVES))
+  if dpenalty is not None:
+    _f32(dpenalty, 'dpenalty', (n,))
+  with torch.cuda.device(x.device):
+    wsp, wsb = _ws_curves(x, curve_steps, workspace)
+    _check(
+        lib.expo_filter_dispatch_curves_bwd(_ptr(ids), _ptr(x), _ptr(dy), _ptr(dx), _ptr(params), _ptr(dparams),
+                                            _ptr(dpenalty), curve_steps, n, h, w, _dtype_code(x), int(hsv_grad_mode), wsp,
+                                            wsb, _stream()), 'expo_filter_dispatch_curves_bwd')
+
+
+def heads_regress_curves_fwd(raws, abi_ids, ranges, selected, params, curve_steps):
+  """heads_regress_fwd for any cfg.curve_steps: params (N, EXPO_MAX_PARAMS_CURVES); a Tone head regresses
+  ``curve_steps`` values, a Color head three times as many."""
+  lib = load()
+  n, h, ptrs, widths, abi, rng = _heads_common(raws, abi_ids, ranges)
+  curve_steps = _curve_steps(curve_steps)
+  _ids(selected, n)
+  _f32(params, 'params', (n, EXPO_MAX_PARAMS_CURVES))
+  with torch.cuda.device(params.device):
+    _check(lib.expo_heads_regress_curves_fwd(ptrs, widths, abi, h, rng, _ptr(selected), _ptr(params), curve_steps, n,
+                                             _stream()), 'expo_heads_regress_curves_fwd')
+
+
+def heads_regress_curves_bwd(raws, draws, abi_ids, ranges, selected, dparams, curve_steps):
+  lib = load()
+  n, h, ptrs, widths, abi, rng = _heads_common(raws, abi_ids, ranges)
+  curve_steps = _curve_steps(curve_steps)
+  assert len(draws) == h and all(d.shape == r.shape and d.is_contiguous() and d.dtype == torch.float32 for d, r in zip(draws, raws))
+  dptrs = (_vp * h)(*[ctypes.c_void_p(d.data_ptr()) for d in draws])
+  _ids(selected, n)
+  _f32(dparams, 'dparams', (n, EXPO_MAX_PARAMS_CURVES))
+  with torch.cuda.device(dparams.device):
+    _check(lib.expo_heads_regress_curves_bwd(ptrs, dptrs, widths, abi, h, rng, _ptr(selected), _ptr(dparams), curve_steps,
+                                             n, _stream()), 'expo_heads_regress_curves_bwd')
 
 
 def chain_streams(n, h, w, dtype_code):

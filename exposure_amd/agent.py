@@ -190,6 +190,9 @@ class Agent(nn.Module):
     # cfg.filters in the C-ABI's own order (both shipped configs): the selected position IS the filter id -- no look-up
     # (compare, clamp, cast, gather, fill, where: six launches per step)
     self._abi_identity = [f.filter_id for f in self.filters] == list(range(len(self.filters)))
+    # opt-in: with a curve filter at cfg.curve_steps != 8 (and cfg.masking off) the step runs the per-image dispatch for
+    # any step count (filters.dispatch_filters_curves) instead of _forward_generic's stack-and-select
+    self.curve_dispatch = False
 
   def pack_heads(self, now=True):
     """Builds the packed storage of the K filter heads (filters.PackedHeads) and, with ``now``, moves the parameters
@@ -255,9 +258,11 @@ class Agent(nn.Module):
     # Training-time fast path (round 4): the regressors and the one-hot gather of the selected filter's parameters as
     # ONE kernel behind the heads' second FCs (filters.heads_regress_select).  Needs what the dispatch kernels need
     # (8-step curves, masking off) and a device; everything else takes the op-by-op path below.
+    generic = any(f.uses_generic_kernels() for f in self.filters)
+    curve_dispatch = bool(self.curve_dispatch) and generic and not cfg.masking
+    curve_steps = int(self.cfg.curve_steps) if curve_dispatch else None
     fused_heads = (not cfg.masking and net.is_cuda and high_res is None and len(self.filters) <= 16 and
-                   not any(f.uses_generic_kernels() for f in self.filters) and
-                   all(type(f) in F.FUSED_HEAD_TYPES for f in self.filters))
+                   (not generic or curve_dispatch) and all(type(f) in F.FUSED_HEAD_TYPES for f in self.filters))
     if fused_heads:
       # the K heads' two FCs as one GEMM + one batched GEMM over parameters packed in place (filters.PackedHeads);
       # EXPO_PACKED_HEADS=0: one addmm / lrelu / addmm per head
@@ -273,7 +278,7 @@ class Agent(nn.Module):
 
     selector_features = self.selector_features(enriched, masks[1], centered=centered, trunk_out=trunk_s)
     if fused_heads and k <= 16 and z.dtype == torch.float32 and states.shape[1] >= 3 + k:
-      return self._forward_fused(net, z, states, raws, selector_features, is_train, progress)
+      return self._forward_fused(net, z, states, raws, selector_features, is_train, progress, curve_steps)
     pdf, entropy = self.action_pdf(selector_features)
     random_filter_id = pdf_sample(pdf, selection_noise)
     max_filter_id = torch.argmax(pdf, dim=1).to(torch.int32)
@@ -282,18 +287,20 @@ class Agent(nn.Module):
     filter_one_hot = (selected_filter_id[:, None] == torch.arange(k, device=net.device)[None, :]).to(pdf.dtype)
     surrogate = (filter_one_hot * torch.log(pdf + 1e-10)).sum(dim=1, keepdim=True)
 
-    if any(f.uses_generic_kernels() for f in self.filters):
+    if generic and not curve_dispatch:
       return self._forward_generic(net, states, params, mask_params, pdf, entropy, selected_filter_id, filter_one_hot,
                                    surrogate, progress, high_res)
+    # (with curve_dispatch the row is the wide one of the dispatch for any cfg.curve_steps, 48 values)
+    width = F._cabi.EXPO_MAX_PARAMS_CURVES if curve_dispatch else F._cabi.EXPO_MAX_PARAMS
     if fused_heads:
-      params24 = F.heads_regress_select(list(self.filters), raws, selected_filter_id)
+      params24 = F.heads_regress_select(list(self.filters), raws, selected_filter_id, curve_steps=curve_steps)
     else:
       # one-hot gather of the selected filter's packed parameters -> (N, 24); same gradient
       # routing as the reference's one-hot product over the stacked images
-      params24 = net.new_zeros((n, F._cabi.EXPO_MAX_PARAMS), dtype=torch.float32)
+      params24 = net.new_zeros((n, width), dtype=torch.float32)
       for j, (filt, p) in enumerate(zip(self.filters, params)):
         pj = filt.pack(p).float()
-        params24 = params24 + torch.nn.functional.pad(pj, (0, F._cabi.EXPO_MAX_PARAMS - pj.shape[1])) * \
+        params24 = params24 + torch.nn.functional.pad(pj, (0, width - pj.shape[1])) * \
             filter_one_hot[:, j:j + 1]
     hsv_mode = int(cfg.get('hsv_grad_mode', 0))
     abi_ids = torch.where(selected_filter_id >= 0, self.abi_filter_ids[selected_filter_id.clamp_min(0).long()],
@@ -309,6 +316,10 @@ class Agent(nn.Module):
       overexposure = F.overexposure_penalty(out)
       if high_res is not None:
         high_res_output = self._apply_masked(high_res, params24, mask6, abi_ids)
+    elif curve_dispatch:
+      out, overexposure = F.dispatch_filters_curves(net, params24, abi_ids, curve_steps, hsv_mode)
+      if high_res is not None:
+        high_res_output, _ = F.dispatch_filters_curves(high_res, params24, abi_ids, curve_steps, hsv_mode)
     else:
       out, overexposure = F.dispatch_filters(net, params24, abi_ids, hsv_mode)
       if high_res is not None:
@@ -324,7 +335,7 @@ class Agent(nn.Module):
         'selected_filter_ids': selected_filter_id,
         'abi_filter_ids': abi_ids,
         'pdf_batch': pdf,
-        'params24': params24,
+        'params48' if curve_dispatch else 'params24': params24,
     }
     if cfg.masking:
       debug_info['mask6'] = mask6  # the selected filter's squashed mask rows: what a replay of this step needs
@@ -432,10 +443,11 @@ def _forward_generic(self, net, states, params, mask_params, pdf, entropy, selec
   return (out, new_states, high_res_output), debug_info, None
 
 
-def _forward_fused(self, net, z, states, raws, selector_features, is_train, progress):
+def _forward_fused(self, net, z, states, raws, selector_features, is_train, progress, curve_steps=None):
   """The training-time step on the device with the glue fused (round 4): selector FCs -> ONE selection kernel
   (_AgentSelect) -> ONE regress-and-gather kernel (filters.heads_regress_select) -> ONE dispatch kernel with the
-  over-exposure penalty.  Same values as the op-by-op path (tests/test_hip_agent.py); cfg.masking off, 8-step curves."""
+  over-exposure penalty.  Same values as the op-by-op path (tests/test_hip_agent.py); cfg.masking off, 8-step curves --
+  or, with ``curve_steps`` (Agent.curve_dispatch), the wide regress-and-gather kernel and the dispatch for any step count."""
   cfg = self.cfg
   k = len(self.filters)
   logits = self.selector_fc2(lrelu(self.selector_fc1(selector_features)))
@@ -443,12 +455,15 @@ def _forward_fused(self, net, z, states, raws, selector_features, is_train, prog
   consts = (cfg.exploration, cfg.exploration_penalty, cfg.filter_usage_penalty, cfg.early_stop_penalty, cfg.test_steps)
   pdf, entropy, selected, one_hot, surrogate, new_states, pen_base = _AgentSelect.apply(
       logits, z, states, prog.reshape(1).float(), consts, int(is_train))
-  params24 = F.heads_regress_select(list(self.filters), raws, selected)
+  params24 = F.heads_regress_select(list(self.filters), raws, selected, curve_steps=curve_steps)
   if self._abi_identity:
     abi_ids = selected
   else:
     abi_ids = torch.where(selected >= 0, self.abi_filter_ids[selected.clamp_min(0).long()], torch.full_like(selected, -1))
-  out, overexposure = F.dispatch_filters(net, params24, abi_ids, int(cfg.get('hsv_grad_mode', 0)))
+  if curve_steps is not None:
+    out, overexposure = F.dispatch_filters_curves(net, params24, abi_ids, curve_steps, int(cfg.get('hsv_grad_mode', 0)))
+  else:
+    out, overexposure = F.dispatch_filters(net, params24, abi_ids, int(cfg.get('hsv_grad_mode', 0)))
   if cfg.clamp:
     out = torch.clamp(out, 0.0, 5.0)
     overexposure = F.overexposure_penalty(out)
@@ -461,7 +476,7 @@ def _forward_fused(self, net, z, states, raws, selector_features, is_train, prog
       'selected_filter_ids': selected,
       'abi_filter_ids': abi_ids,
       'pdf_batch': pdf,
-      'params24': params24,
+      'params48' if curve_steps is not None else 'params24': params24,
   }
   return (out, new_states, surrogate, penalty), debug_info, None
 

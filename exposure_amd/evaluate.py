@@ -868,6 +868,10 @@ def main(argv=None):
                   help='with --curve-steps L != 8: apply the steps in the one fused pass for any L (fp32 between steps, '
                   'taps, --batch in one ragged launch) instead of step by step.  Not with --stepwise; --masking keeps '
                   'the stepwise schedule; no effect with 8-step curves')
+  ap.add_argument('--curve-dispatch', action='store_true',
+                  help="with --curve-steps L != 8: the agent's own 64x64 step on the per-image dispatch kernels for any L "
+                  '(Agent.curve_dispatch) instead of running every filter on the whole batch; with or without '
+                  '--fused-curves; --masking keeps the stack-and-select step; no effect with 8-step curves')
   ap.add_argument('--batch', type=int, default=1, metavar='N',
                   help='retouch up to N images at once, of any sizes, grouped in argument order (retouch_batch: the '
                   'agent runs on the stacked proxies, one ragged launch applies the filters).  z and the dropout '
@@ -926,6 +930,7 @@ def main(argv=None):
   if args.fused_curves and args.stepwise:
     ap.error('--fused-curves does not go with --stepwise: they are two schedules of the full-resolution pass')
   agent = Agent(cfg).to(dev)
+  agent.curve_dispatch = bool(args.curve_dispatch)
   if args.weights and args.tf_checkpoint:
     ap.error('--weights and --tf-checkpoint are alternatives')
   if args.weights:

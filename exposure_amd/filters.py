@@ -197,15 +197,50 @@ class _HeadsRegressSelect(torch.autograd.Function):
     return (None, None, None) + tuple(draws)
 
 
-def heads_regress_select(filter_modules, raws, selected):
+class _HeadsRegressSelectCurves(torch.autograd.Function):
+  """_HeadsRegressSelect for any cfg.curve_steps -- ``expo_heads_regress_curves_fwd / _bwd``: rows of
+  EXPO_MAX_PARAMS_CURVES values, a Tone head of L and a Color head of 3 L of them."""
+
+  @staticmethod
+  def forward(ctx, selected, abi_ids, ranges, curve_steps, *raws):
+    raws = tuple(r.contiguous().float() for r in raws)
+    n = raws[0].shape[0]
+    params = torch.empty((n, _cabi.EXPO_MAX_PARAMS_CURVES), dtype=torch.float32, device=raws[0].device)
+    selected = selected.contiguous().to(torch.int32)
+    _cabi.heads_regress_curves_fwd(raws, abi_ids, ranges, selected, params, curve_steps)
+    ctx.save_for_backward(selected, *raws)
+    ctx.meta = (tuple(abi_ids), tuple(ranges), int(curve_steps))
+    return params
+
+  @staticmethod
+  def backward(ctx, dparams):
+    selected, *raws = ctx.saved_tensors
+    abi_ids, ranges, curve_steps = ctx.meta
+    n = raws[0].shape[0]
+    # one flat buffer, head-major, as in _HeadsRegressSelect
+    widths = [r.shape[1] for r in raws]
+    flat = torch.empty((n * sum(widths),), dtype=torch.float32, device=raws[0].device)
+    draws, at = [], 0
+    for w in widths:
+      draws.append(flat[at:at + n * w].view(n, w))
+      at += n * w
+    _cabi.heads_regress_curves_bwd(raws, draws, abi_ids, ranges, selected, dparams.contiguous().float(), curve_steps)
+    return (None, None, None, None) + tuple(draws)
+
+
+def heads_regress_select(filter_modules, raws, selected, curve_steps=None):
   """The fused tail of the FC heads (see _HeadsRegressSelect).  ``filter_modules``: the agent's Filter list (their
-  ``filter_id`` and ``cfg`` ranges), ``raws``: each head's second-FC output (N, P_j + 6), ``selected`` (N,) int32."""
+  ``filter_id`` and ``cfg`` ranges), ``raws``: each head's second-FC output (N, P_j + 6), ``selected`` (N,) int32.
+  With ``curve_steps`` the wide path for any cfg.curve_steps: -> (N, EXPO_MAX_PARAMS_CURVES)."""
   cfg = filter_modules[0].cfg
   tl, tr = cfg.tone_curve_range
   cl, cr = cfg.color_curve_range
   bias = lambda l, r, initial: math.atanh(2 * (initial - l) / (r - l) - 1) if initial is not None else 0.0
   ranges = (float(cfg.exposure_range), math.log(cfg.gamma_range), float(tl), float(tr), 0.0, float(cl), float(cr),
             bias(cl, cr, 1), bias(-cfg.exposure_range, cfg.exposure_range, 0))
+  if curve_steps is not None:
+    return _HeadsRegressSelectCurves.apply(selected, tuple(int(f.filter_id) for f in filter_modules), ranges,
+                                           int(curve_steps), *raws)
   return _HeadsRegressSelect.apply(selected, tuple(int(f.filter_id) for f in filter_modules), ranges, *raws)
 
 
@@ -854,6 +889,40 @@ def dispatch_filters(img, params24, filter_ids, hsv_grad_mode=0):
   first P slots.  Returns (y, overexposure_penalty[N]) -- the latter is agent.py:249-251's
   ``reduce_mean(maximum(net - 1, 0)**2, axis=(1,2,3))``."""
   return _DispatchFunction.apply(img, params24, filter_ids, hsv_grad_mode)
+
+
+class _DispatchCurvesFunction(torch.autograd.Function):
+  """_DispatchFunction for any cfg.curve_steps (expo_filter_dispatch_curves_fwd/bwd): 48-wide parameter rows."""
+
+  @staticmethod
+  def forward(ctx, img, params48, filter_ids, curve_steps, hsv_grad_mode):
+    img = img.contiguous()
+    params48 = params48.contiguous().float()
+    filter_ids = filter_ids.contiguous().to(torch.int32)
+    y = torch.empty_like(img)
+    penalty = torch.empty((img.shape[0],), dtype=torch.float32, device=img.device)
+    _cabi.dispatch_curves_fwd(filter_ids, img, y, params48, curve_steps, penalty)
+    ctx.save_for_backward(img, params48, filter_ids)
+    ctx.args = (int(curve_steps), hsv_grad_mode)
+    return y, penalty
+
+  @staticmethod
+  def backward(ctx, dy, dpenalty):
+    img, params48, filter_ids = ctx.saved_tensors
+    curve_steps, hsv_grad_mode = ctx.args
+    dy = dy.contiguous().to(img.dtype)
+    dpenalty = dpenalty.contiguous().float()
+    dx = torch.empty_like(img) if ctx.needs_input_grad[0] else None
+    dparams = torch.empty_like(params48)
+    _cabi.dispatch_curves_bwd(filter_ids, img, dy, dx, params48, dparams, curve_steps, dpenalty, hsv_grad_mode)
+    return dx, dparams, None, None, None
+
+
+def dispatch_filters_curves(img, params48, filter_ids, curve_steps, hsv_grad_mode=0):
+  """:func:`dispatch_filters` for any cfg.curve_steps: params48 (N, EXPO_MAX_PARAMS_CURVES) float32, row n = the packed
+  parameters of filter ``filter_ids[n]`` at its front (Tone: ``curve_steps`` knots, Color: channel * curve_steps + knot).
+  Returns (y, overexposure_penalty[N])."""
+  return _DispatchCurvesFunction.apply(img, params48, filter_ids, int(curve_steps), hsv_grad_mode)
 
 
 class _FusedSequenceFunction(torch.autograd.Function):

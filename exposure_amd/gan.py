@@ -26,7 +26,7 @@ from .util import STATE_STEP_DIM, STATE_STOPPED_DIM, capture_without_gc
 class GAN(nn.Module):
 
   def __init__(self, cfg, device=None, process_group=None, use_graphs=False, seed=0, direct_critic=True,
-               direct_generator=True):
+               direct_generator=True, curve_dispatch=False):
     super().__init__()
     self.cfg = cfg
     self.use_graphs = bool(use_graphs)
@@ -39,6 +39,9 @@ class GAN(nn.Module):
     self.direct_generator = bool(direct_generator)
     self._graphs = {}
     self.generator = Agent(cfg)
+    # opt-in (Agent.curve_dispatch): with cfg.curve_steps != 8 the agent's step on the per-image dispatch kernels for any
+    # step count instead of the stack-and-select path
+    self.generator.curve_dispatch = bool(curve_dispatch)
     self.critic = Critic(cfg, num_state_dim=0)
     self.value = Critic(cfg, num_state_dim=cfg.num_state_dim)
     if device is not None:

@@ -39,6 +39,10 @@ def parse_args(argv=None):
   ap.add_argument('--curve-steps', type=int, default=None, metavar='L',
                   help='cfg.curve_steps, 1..16 (default 8): the knots of the Tone and Color curves (L != 8 trains on '
                   'the generic curve kernels)')
+  ap.add_argument('--curve-dispatch', action='store_true',
+                  help='with --curve-steps other than 8: the agent\'s step on the per-image dispatch kernels for any step '
+                  'count (one selection, one regress-and-gather and one dispatch launch each way) instead of running '
+                  'every filter on the whole batch')
   ap.add_argument('--dtype', default='f32', choices=['f32', 'f16'], help='storage type of the image pool')
   ap.add_argument('--fake-dir', default=None, help='folder of input photos (with --real-dir; default: synthetic data)')
   ap.add_argument('--real-dir', default=None, help='folder of target photos (with --fake-dir)')
@@ -95,7 +99,7 @@ def main(argv=None):
   cfg.clamp = bool(args.clamp)
   if args.curve_steps is not None:
     cfg.curve_steps = args.curve_steps
-  gan = GAN(cfg, device=dev, use_graphs=not args.no_graphs, seed=args.seed)  # (--seed also drives dropout / alpha)
+  gan = GAN(cfg, device=dev, use_graphs=not args.no_graphs, seed=args.seed, curve_dispatch=args.curve_dispatch)  # (--seed also drives dropout / alpha)
   dt = torch.float32 if args.dtype == 'f32' else torch.float16
   if args.fake_dir is not None:
     fake, real = photo_providers(args, cfg, dev, dt)

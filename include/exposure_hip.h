@@ -782,6 +782,50 @@ int expo_curve_bwd(const void* x, const void* dy, void* dx, const float* params,
                    int w, int dtype, int curves, int steps, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * (added exports, ABI 9) The per-image dispatch and the heads' tail for ANY cfg.curve_steps: what
+ * expo_filter_dispatch_fwd / _bwd and expo_heads_regress_fwd / _bwd are at 8 steps, with
+ *   params / dparams  float32 [N][EXPO_MAX_PARAMS_CURVES];
+ *   curve_steps       L in [1, EXPO_CURVE_MAX_STEPS], one value for the call;
+ *   ids 4 and 7       the curves of expo_curve_fwd / _bwd with `steps` = L: a Tone row holds k_0..k_{L-1}, a Color row
+ *                     channel * L + knot -- the layout expo_chain_fused_curves_fwd_ragged takes;
+ *   every other id    (0-3, 5, 6, 8, and -1 = nothing selected) exactly as in expo_filter_dispatch_*, on the first
+ *                     slots of the row: the same kernel bodies, the same image and image-gradient bits.
+ * Nothing behind a filter's parameters is read.  An id outside [-1, 8] selects nothing, like -1 (the ids live on the
+ * device: they are not validated on the host).
+ * expo_filter_dispatch_curves_fwd: one streaming launch; `penalty` (nullable, float32 [N]) is the fused over-exposure
+ *   term mean max(y - 1, 0)^2 and costs one finish launch and the workspace.
+ * expo_filter_dispatch_curves_bwd: dparams is fully overwritten (zeros behind a filter's parameters and in rows with
+ *   id -1); dx nullable; dpenalty nullable (the same bits as a dpenalty of zeros: the kernels with the fused penalty
+ *   run with a zero scale, so without it the light rows need not have expo_filter_dispatch_bwd's bits, which come from
+ *   other instantiations of the bodies), its share 2 max(y - 1, 0) / (H W 3) dpenalty[n] is added to dy first.  Curve
+ *   gradients follow expo_curve_bwd (both clip bounds inclusive, both neighbouring slopes on a knot).  Two streaming
+ *   launches -- light filters, curves; an image outside a launch's set costs that launch one early exit per block --
+ *   and one finish launch.  No float atomics: block records and a fixed-order finish, bit-reproducible.  The curve
+ *   launch keeps 3 (2 L + 1) private accumulator columns per thread in dynamic LDS, sized from L.
+ * expo_filter_dispatch_curves_workspace_bytes: bytes both directions need (0 for invalid arguments); grows with L, and
+ *   holds one image tensor of scratch: dparams has the same bits with and without dx, so the light launch always
+ *   stores dx -- compiled without the store three of the tuned bodies round their parameter gradients differently.
+ * expo_heads_regress_curves_fwd / _bwd: a Tone head regresses L values, a Color head 3 L; ranges, biases, the -1
+ *   convention and "d raw is zero outside the selected head's parameter slice" as in expo_heads_regress_*.
+ * Validated before anything is enqueued (EXPO_E_BADARG / EXPO_E_BADDTYPE): curve_steps, shapes, dtype, null pointers,
+ * a null / misaligned / short workspace, hsv_grad_mode, the heads' count, widths and filter ids; n == 0 is a no-op.
+ */
+size_t expo_filter_dispatch_curves_workspace_bytes(int n, int h, int w, int dtype, int curve_steps);
+int expo_filter_dispatch_curves_fwd(const int32_t* filter_ids, const void* x, void* y, const float* params,
+                                    int curve_steps, float* penalty, int n, int h, int w, int dtype, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int expo_filter_dispatch_curves_bwd(const int32_t* filter_ids, const void* x, const void* dy, void* dx,
+                                    const float* params, float* dparams, const float* dpenalty, int curve_steps, int n,
+                                    int h, int w, int dtype, int hsv_grad_mode, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int expo_heads_regress_curves_fwd(const float* const* raw, const int* widths, const int* abi_ids, int heads,
+                                  const float* ranges, const int32_t* selected, float* params, int curve_steps, int n,
+                                  void* stream);
+int expo_heads_regress_curves_bwd(const float* const* raw, float* const* draw, const int* widths, const int* abi_ids,
+                                  int heads, const float* ranges, const int32_t* selected, const float* dparams,
+                                  int curve_steps, int n, void* stream);
+
+/*
  * One Adam update of a LIST of fp32 tensors in one launch -- the three optimisers of a training iteration
  * (net.py:222-251 `ly.optimize_loss(..., optimizer=cfg.optimizer)`; config_example.py:158
  * `tf.train.AdamOptimizer(learning_rate=lr, beta1=0.5, beta2=0.9)`), replacing torch's fused multi-tensor Adam
