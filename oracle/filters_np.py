@@ -2,7 +2,10 @@
 
 TEST INFRASTRUCTURE ONLY (see ``oracle/__init__.py``); PARITY UNPINNED by the
 reference (it has no tests) -- pinned by identities / known answers / finite
-differences in ``tests/test_oracle_filters.py``.
+differences in ``tests/test_oracle_filters.py``, and forward and backward by
+the executed bodies of the reference's methods under a stand-in ``tf``
+(``tests/golden/reference_facade.npz``, ``reference_grad_facade.npz``:
+composition pins, TF primitive semantics and gradients assumed).
 
 Every function cites the reference lines it follows (paths relative to
 ``/root/reference``).  Images are NHWC ``(N, H, W, 3)``.  Arithmetic runs in the
@@ -22,7 +25,9 @@ Two parameter conventions are provided:
 
 The backward functions are hand-derived (they are what the HIP kernels
 implement); ``oracle/filters_torch.py`` obtains the same gradients from
-autograd on an op-by-op transcription, and the tests require both to agree.
+autograd on an op-by-op transcription, and the tests require both to agree --
+and both to agree with autograd through the reference's own statements
+(``tests/test_reference_grad_facade.py``, to 1e-10, tie pixels included).
 TF gradient conventions encoded here: ``tf.maximum(x, c)`` / ``tf.minimum(x,
 c)`` pass the gradient to ``x`` on equality, ``tf.clip_by_value`` passes on
 ``lo <= x <= hi`` (both inclusive), ``abs'(0) = 0``, and TF-1.x registers

@@ -10,7 +10,7 @@ selection / state / penalty statements of agent_generator, agent.py:100-123, 208
 
 It pins how the restatements COMPOSE the primitives (operand order, broadcast axes, which tensor is clamped before which
 blend, knot indexing, the epsilon guards, exclusive-cumsum sampling incl. id -1 at noise 0) -- not the primitives (the
-facade's own clip / maximum / HSV are stand-ins), and no gradient."""
+facade's own clip / maximum / HSV are stand-ins).  The gradients of the same bodies: tests/test_reference_grad_facade.py."""
 import os
 
 import numpy as np
