@@ -107,6 +107,9 @@ SIGNATURES = {
     'expo_chain_fused_fwd_ragged_codes': (_i, [_vp, _fp, _i, ctypes.POINTER(_vp), _i, _i, _vp, _i, ctypes.POINTER(_vp),
                                                ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.c_uint64, _i,
                                                ctypes.POINTER(_vp), _vp]),
+    'expo_chain_fused_curves_fwd_ragged_codes': (_i, [_vp, _fp, _i, _i, ctypes.POINTER(_vp), _i, _i, _vp, _i,
+                                                      ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
+                                                      ctypes.c_uint64, _i, ctypes.POINTER(_vp), _vp]),
     'expo_codes_max_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _vp, _vp, _sz,
                                    _vp]),
     'expo_codes_lut_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _vp, _i, _i,
@@ -881,12 +884,9 @@ def bilinear_resize_ragged_codes(codes, tables, stride, windows, S, out):
   return out
 
 
-def chain_fused_fwd_ragged_codes(filter_ids, params, codes, tables, stride, ys, tap_mask=0, taps=None):
-  """``chain_fused_fwd_ragged_taps`` with the input of image i given as its integer codes plus its table
-  (``expo_chain_fused_fwd_ragged_codes``): codes as in ``decode_ragged``, tables / stride from ``decode_tables`` in the
-  storage dtype.  ys: N contiguous device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3) of the tables' dtype, or None (taps
-  only); tap_mask may be 0 (taps None); taps as in ``chain_fused_fwd_ragged_taps``."""
-  lib = load()
+def _ragged_codes_args(filter_ids, params, codes, tables, stride, ys, tap_mask, taps, width=EXPO_MAX_PARAMS):
+  """The checks the fused passes from integer codes share -> (steps, device, code bits, channels, hs, ws, dtype code,
+  stride, tap format, tap count), or None for an empty list.  `width`: the floats of a parameter row."""
   n = len(codes)
   if ys is not None and len(ys) != n:
     raise ExposureHipError('exposure_amd: codes and ys must have the same length')
@@ -896,14 +896,14 @@ def chain_fused_fwd_ragged_codes(filter_ids, params, codes, tables, stride, ys, 
       not filter_ids.is_contiguous():
     raise ExposureHipError('exposure_amd: filter_ids must be a contiguous int32 device tensor of shape (N, steps)')
   steps = filter_ids.shape[1]
-  _f32(params, 'params', (n, steps, EXPO_MAX_PARAMS))
+  _f32(params, 'params', (n, steps, width))
   t = _tap_count(tap_mask, steps)
   if ys is None and not t:
     raise ExposureHipError('exposure_amd: nothing to write (ys None and tap_mask 0)')
   if t and taps is None:
     raise ExposureHipError('exposure_amd: tap_mask 0x%x needs taps' % tap_mask)
   if n == 0:
-    return
+    return None
   dev = filter_ids.get_device()
   if params.get_device() != dev:
     raise ExposureHipError('exposure_amd: filter_ids and params must be on the images\' device')
@@ -930,12 +930,52 @@ def chain_fused_fwd_ragged_codes(filter_ids, params, codes, tables, stride, ys, 
           tp.get_device() != dev or not tp.is_contiguous():
         raise ExposureHipError('exposure_amd: taps[%d] must be a contiguous device tensor (%d, %d, %d, 3) of the '
                                'dtype of taps[0]' % (i, t, h, w))
+  return steps, dev, bits, c, hs, ws, dtc, stride, fmt, t
+
+
+def chain_fused_fwd_ragged_codes(filter_ids, params, codes, tables, stride, ys, tap_mask=0, taps=None):
+  """``chain_fused_fwd_ragged_taps`` with the input of image i given as its integer codes plus its table
+  (``expo_chain_fused_fwd_ragged_codes``): codes as in ``decode_ragged``, tables / stride from ``decode_tables`` in the
+  storage dtype.  ys: N contiguous device tensors (H_i, W_i, 3) or (1, H_i, W_i, 3) of the tables' dtype, or None (taps
+  only); tap_mask may be 0 (taps None); taps as in ``chain_fused_fwd_ragged_taps``."""
+  lib = load()
+  args = _ragged_codes_args(filter_ids, params, codes, tables, stride, ys, tap_mask, taps)
+  if args is None:
+    return
+  steps, dev, bits, c, hs, ws, dtc, stride, fmt, t = args
+  n = len(codes)
   with torch.cuda.device(dev):
     _check(lib.expo_chain_fused_fwd_ragged_codes(_ptr(filter_ids), _ptr(params), steps, _ptr_array(codes), c, bits,
                                                  _ptr(tables), stride, None if ys is None else _ptr_array(ys),
                                                  (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, dtc, tap_mask, fmt,
                                                  None if not t else _ptr_array(taps), _stream()),
            'expo_chain_fused_fwd_ragged_codes')
+
+
+def chain_fused_curves_fwd_ragged_codes(filter_ids, params48, curve_steps, codes, tables, stride, ys, tap_mask=0,
+                                        taps=None):
+  """``chain_fused_curves_fwd_ragged`` with the input of image i given as its integer codes plus its table
+  (``expo_chain_fused_curves_fwd_ragged_codes``): ``chain_fused_fwd_ragged_codes`` for any cfg.curve_steps.  params48
+  (N, steps, EXPO_MAX_PARAMS_CURVES) float32 and curve_steps = L in [1, EXPO_CURVE_MAX_STEPS] as in
+  ``chain_fused_curves_fwd_ragged``; codes, tables, stride, ys, tap_mask and taps as in
+  ``chain_fused_fwd_ragged_codes``, with the same checks.  The result has the bits of ``decode_ragged`` followed by
+  ``chain_fused_curves_fwd_ragged``."""
+  lib = load()
+  curve_steps = int(curve_steps)
+  if not 1 <= curve_steps <= EXPO_CURVE_MAX_STEPS:
+    raise ExposureHipError('exposure_amd: curve_steps must be in [1, %d], got %d' % (EXPO_CURVE_MAX_STEPS, curve_steps))
+  args = _ragged_codes_args(filter_ids, params48, codes, tables, stride, ys, tap_mask, taps, EXPO_MAX_PARAMS_CURVES)
+  if args is None:
+    return
+  steps, dev, bits, c, hs, ws, dtc, stride, fmt, t = args
+  n = len(codes)
+  with torch.cuda.device(dev):
+    _check(lib.expo_chain_fused_curves_fwd_ragged_codes(_ptr(filter_ids), _ptr(params48), steps, curve_steps,
+                                                        _ptr_array(codes), c, bits, _ptr(tables), stride,
+                                                        None if ys is None else _ptr_array(ys), (ctypes.c_int * n)(*hs),
+                                                        (ctypes.c_int * n)(*ws), n, dtc, tap_mask, fmt,
+                                                        None if not t else _ptr_array(taps), _stream()),
+           'expo_chain_fused_curves_fwd_ragged_codes')
 
 
 def codes_max_ragged(codes, workspace=None):

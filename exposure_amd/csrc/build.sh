@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
-# Fifteen translation units plus chain_fused_curves.hip, the sixteenth, and dispatch_curves.hip, the seventeenth; extra
-# arguments go to every compile step.
+# Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
+# chain_fused_curves_codes.hip, the eighteenth; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
@@ -27,6 +27,9 @@
 #   metric.hip           the evaluation metric's patch statistics and their histograms (default flags)
 #   dispatch_curves.hip  the agent's per-image dispatch step and its head regressors for any cfg.curve_steps (the flags
 #                        of exposure_hip.hip: the light filters' bodies must give that unit's bits)
+#   chain_fused_curves_codes.hip  the fused inference pass for any cfg.curve_steps reading the files' integer codes
+#                        (exactly chain_fused.hip's flags: the step loop of chain_fused_curves.hip behind the loader of
+#                        chain_fused_codes.hip, bit for bit decode + that pass)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -71,6 +74,8 @@ p15=$!
 p16=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/dispatch_curves.hip" -o "$TMP/dispatch_curves.o" &
 p17=$!
+"$HIPCC" "${FLAGS[@]}" -fno-slp-vectorize -fno-honor-nans "$@" -c "$HERE/chain_fused_curves_codes.hip" -o "$TMP/chain_fused_curves_codes.o" &
+p18=$!
 wait $p1
 wait $p2
 wait $p3
@@ -88,5 +93,6 @@ wait $p14
 wait $p15
 wait $p16
 wait $p17
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" -o "$OUT"
+wait $p18
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -8,34 +8,20 @@
 // chain_fused_run, TapSink and the stores, which it uses untouched, and instantiates none of its kernels
 // (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), so the kernels of chain_fused.hip keep their code and registers and the two units
 // compile side by side.  The only device code of its own is the loader below (the row load is codes_loader.h's).
-//   vector path       a lane's group keeps pixel_io.h's pixel positions: row r of a wave's chunk is the 12-byte vector
-//                     of PPV pixels (fp16 2, fp32 1) at pixel gw * PPL + r * 64 * PPV + lane * PPV; its PPV * C codes
-//                     come in with the widest buffer load their size allows, as decode_kernel's.  Rows past the end of
-//                     the image read code 0 and their stores are dropped by the bounds checks.
-//   element-wise path per image, block-uniform: codes not 4-byte aligned, hw % PPV != 0, or y / a vector-stored tap
-//                     plane misaligned (the rule of chain_fused.hip with the codes' base added).
+// The table of a launch, the argument checks and the split into launches are codes_image.h's, shared with
+// chain_fused_curves_codes.hip.  The loader below is stated here and, word for word, as codes_image_loop in that header
+// for the other unit: calling the header's from here moves this unit's instruction schedule, and its listing is held
+// fixed.
 //   tables            an 8-bit table is staged in LDS once per block (a block belongs to one image; 512 B / 1 KiB); a
 //                     16-bit table (128 / 256 KiB per image) is read through the caches.
 #define EXPO_CHAIN_FUSED_TEMPLATES_ONLY
 #include "chain_fused.hip"
-#include "codes_loader.h"
+#include "codes_image.h"
 
 namespace expo {
 
 namespace {
 
-// up to 64 images by value in the kernel arguments (2 KB): codes, output (NULL: none), tap buffer, pixel count, first
-// block of each image (first[n] = the grid's size) and a bit per image for the vector path
-template <typename T>
-struct CodesTable {
-  const void* codes[kRaggedMaxImages];
-  T* y[kRaggedMaxImages];
-  char* taps[kRaggedMaxImages];
-  int hw[kRaggedMaxImages];
-  int first[kRaggedMaxImages + 1];
-  int n;
-  uint64_t vec;
-};
 // kernel arguments: ids, params, steps, tap_mask, tables, table_stride, the table
 static_assert(sizeof(CodesTable<half_t>) + 48 <= 4096, "the codes table must fit the 4 KB kernarg block");
 
@@ -156,42 +142,18 @@ template <typename CT, int C, typename T, int FMT>
 int chain_fused_codes_t(const int32_t* ids, const float* params, int steps, const void* const* codes, const void* tables,
                         int table_stride, void* const* ys, const int* hs, const int* ws, int n, uint64_t tap_mask,
                         void* const* taps, hipStream_t s) {
-  constexpr int PPL = PixTraits<T>::PPL;
-  long bytes = 0;  // cache policy from the bytes of the whole call, as the pass from tensors
-  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
-  const bool stream = bytes >= stream_min_bytes();
-  for (int base = 0; base < n; base += kRaggedMaxImages) {
-    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
-    CodesTable<T> tab = {};
-    tab.n = m;
-    long blocks = 0;
-    for (int j = 0; j < m; ++j) {
-      const int i = base + j, hw = hs[i] * ws[i];
-      tab.codes[j] = codes[i];
-      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
-      tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
-      tab.hw[j] = hw;
-      tab.first[j] = int(blocks);
-      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
-      const uintptr_t a = reinterpret_cast<uintptr_t>(codes[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
-                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
-      if (hw % VecTraits<T>::PPV == 0 && (a & 3) == 0) tab.vec |= uint64_t(1) << j;
-    }
-    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
-    tab.first[m] = int(blocks);
-    const int32_t* idb = ids + size_t(base) * steps;
-    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
-    const T* tb = static_cast<const T*>(tables) + size_t(base) * size_t(table_stride);
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
-    if (stream)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoStream, FMT>), grid, block, 0, s, idb, prb, steps,
-                         tap_mask, tb, table_stride, tab);
-    else
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoCached, FMT>), grid, block, 0, s, idb, prb, steps,
-                         tap_mask, tb, table_stride, tab);
-    HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged_codes launch");
-  }
-  return EXPO_OK;
+  return codes_launches<T, FMT>(
+      ids, params, steps, EXPO_MAX_PARAMS, codes, tables, table_stride, ys, hs, ws, n, taps,
+      "chain_fused_fwd_ragged_codes launch",
+      [&](bool stream, dim3 grid, const int32_t* idb, const float* prb, const T* tb, const CodesTable<T>& tab) {
+        const dim3 block(kThreads);
+        if (stream)
+          hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoStream, FMT>), grid, block, 0, s, idb, prb,
+                             steps, tap_mask, tb, table_stride, tab);
+        else
+          hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoCached, FMT>), grid, block, 0, s, idb, prb,
+                             steps, tap_mask, tb, table_stride, tab);
+      });
 }
 
 template <typename CT, int C, typename T>
@@ -232,26 +194,11 @@ int expo_chain_fused_fwd_ragged_codes(const int32_t* filter_ids, const float* pa
                                       int table_stride, void* const* ys, const int* hs, const int* ws, int n, int dtype,
                                       uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
   // everything is checked before the first launch is enqueued
-  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
-  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
-  if (channels != 1 && channels != 3 && channels != 4) return fail(EXPO_E_BADARG, "channels must be 1, 3 or 4");
-  if (code_bits != 8 && code_bits != 16) return fail(EXPO_E_BADARG, "code_bits must be 8 or 16");
-  if (table_stride != 0 && table_stride < (1 << code_bits))
-    return fail(EXPO_E_BADARG, "table_stride must be 0 (one shared table) or at least 2^code_bits entries");
-  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
-  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
-  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
-  if (n == 0) return EXPO_OK;
-  if (!codes || !tables || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
-    return fail(EXPO_E_BADARG, "null pointer");
-  if ((reinterpret_cast<uintptr_t>(tables) & 3) != 0) return fail(EXPO_E_BADARG, "tables must be 4-byte aligned");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
-    if (long(hs[i]) * ws[i] * channels * (code_bits / 8) > (1L << 31) - 8192)
-      return fail(EXPO_E_BADARG, "the codes of one image must be smaller than 2 GiB");
-    if (!codes[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
-    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
-  }
+  bool go;
+  if (int rc = codes_check_args(filter_ids, params, steps, codes, channels, code_bits, tables, table_stride, ys, hs, ws, n,
+                                dtype, tap_mask, tap_format, taps, &go))
+    return rc;
+  if (!go) return EXPO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (code_bits == 8)
     return chain_fused_codes_channels<uint8_t>(channels, dtype, tap_mask, tap_format, filter_ids, params, steps, codes,

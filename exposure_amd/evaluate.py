@@ -588,7 +588,7 @@ def stage_raws(raws, dtype, device):
 
 @torch.no_grad()
 def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_masks=None, return_trace=False,
-                      intermediates=None, picture=False, outputs=True, staged=None):
+                      intermediates=None, picture=False, outputs=True, staged=None, curves='stepwise'):
   """``retouch_batch(agent, decode_images(raws, dtype, device), proxy='device', ...)`` without the decoded tensors
   (DESIGN.md §3.23): ``raws`` are ``load_raw`` results, and the integer codes are what the device reads.  Per
   (kind, channels) group of the batch ``_cabi.decode_tables`` writes the tables ``decode_ragged`` would gather from
@@ -597,19 +597,30 @@ def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_ma
   ``_cabi.chain_fused_fwd_ragged_codes`` launch per group applies that group's rows of ids and params to the codes.
   Every returned value is bit for bit the one of the call above.
 
+  ``curves='fused'`` serves an agent with generic curve filters (a ``cfg.curve_steps`` other than 8)
+  the same way: the agent records its 48-wide rows (``_agent_steps(..., generic=True, params48=...)``, as
+  ``retouch_batch`` does for ``curves='fused'``) and one ``_cabi.chain_fused_curves_fwd_ragged_codes`` launch per group
+  applies them.  Every returned value is then bit for bit the one of
+  ``retouch_batch(agent, decode_images(raws, dtype, device), proxy='device', curves='fused', ...)``.  With an 8-step
+  agent ``curves`` has no effect.
+
   ``outputs=False`` allocates no float output: the first entry is a list of ``None`` (it needs ``picture`` or
   ``intermediates``: something must be written).  ``cfg.masking``, or a ``cfg.curve_steps`` that needs the generic
-  kernels, raises ``ValueError``: there is no pass from codes for them and no silent fallback."""
+  kernels under the default ``curves='stepwise'``, raises ``ValueError``: there is no pass from codes for them and no
+  silent fallback."""
   from . import _cabi
   cfg = agent.cfg
   if intermediates not in INTERMEDIATES:
     raise ValueError('intermediates must be one of %s' % (INTERMEDIATES,))
+  if curves not in CURVES:
+    raise ValueError('curves must be one of %s' % (CURVES,))
   kind = _picture_kind(picture, intermediates)
   if cfg.masking:
     raise ValueError('retouch_batch_raw: cfg.masking has no pass from codes (decode_images + retouch_batch)')
-  if any(f.uses_generic_kernels() for f in agent.filters):
-    raise ValueError('retouch_batch_raw: cfg.curve_steps = %s needs the generic kernels, which have no pass from codes '
-                     '(decode_images + retouch_batch)' % (cfg.curve_steps,))
+  generic = any(f.uses_generic_kernels() for f in agent.filters)
+  if generic and curves != 'fused':
+    raise ValueError('retouch_batch_raw: cfg.curve_steps = %s needs the generic kernels, which have no step-by-step '
+                     'pass from codes (curves=\'fused\', or decode_images + retouch_batch)' % (cfg.curve_steps,))
   raws = list(raws)
   n = len(raws)
   if n == 0:
@@ -629,8 +640,10 @@ def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_ma
     if part is not low:
       low[torch.tensor(idx, device=dev)] = part
     groups.append((idx, cs, tables, stride))
-  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(agent, low, z, steps, dropout_masks)
-  ids, prm = torch.stack(abi_ids, dim=1), torch.stack(params, dim=1)
+  wide = []
+  low, states, _hi, trace, abi_ids, params, stops, _his = _agent_steps(
+      agent, low, z, steps, dropout_masks, generic=generic, params48=wide if generic else None)
+  ids, prm = torch.stack(abi_ids, dim=1), torch.stack(wide if generic else params, dim=1)
   mask, last = _intermediate_mask(stops), 1 << (len(stops) - 1)
   # the taps of a launch have one format: with storage intermediates the pictures are encoded from the outputs
   encode = kind and intermediates == 'storage'
@@ -650,14 +663,17 @@ def retouch_batch_raw(agent, raws, dtype, device, steps=None, z=None, dropout_ma
     tp = [torch.empty((t, c.shape[0], c.shape[1], 3), dtype=tap_dtype, device=dev) for c in cs] if t else None
     sel = torch.tensor(idx, device=dev)
     whole = len(idx) == n
-    _cabi.chain_fused_fwd_ragged_codes(ids if whole else ids[sel].contiguous(), prm if whole else prm[sel].contiguous(),
-                                       cs, tables, stride, ys, tap_mask, tp)
+    gi, gp = (ids, prm) if whole else (ids[sel].contiguous(), prm[sel].contiguous())
+    if generic:  # the same launch for this cfg.curve_steps
+      _cabi.chain_fused_curves_fwd_ragged_codes(gi, gp, cfg.curve_steps, cs, tables, stride, ys, tap_mask, tp)
+    else:
+      _cabi.chain_fused_fwd_ragged_codes(gi, gp, cs, tables, stride, ys, tap_mask, tp)
     for j, i in enumerate(idx):
       if outputs:
         outs[i] = ys[j]
       if t:
         taps[i] = tp[j]
-  res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace)
+  res = _trace_result(outs, low, states, trace, abi_ids, params, return_trace, params48=wide)
   if kind and not encode:
     if intermediates:
       res += ([tp if mask & last else tp[:-1] for tp in taps],)
@@ -891,6 +907,12 @@ def main(argv=None):
                   "images' tables as they load, and the decoded float input is never made.  The same files and records "
                   'as --device-decode --device-proxy, which it implies.  Not with --stepwise or --masking; '
                   '--show-input / --show-linear need --device-input-png (the host pictures need the float input)')
+  ap.add_argument('--fused-decode-curves', action='store_true',
+                  help='--fused-decode for any --curve-steps: with L != 8 the one pass from the integer codes is the '
+                  'one for any L (retouch_batch_raw with curves=\'fused\'), so it is --fused-decode --fused-curves in '
+                  'one switch, and writes the same files and records as --device-decode --device-proxy --fused-curves.  '
+                  'With 8-step curves it is --fused-decode.  Not with --stepwise or --masking; goes with everything '
+                  '--fused-decode goes with')
   ap.add_argument('--pictures-only', action='store_true',
                   help='write no .npy: only the pictures (needs --device-png, --tiff16 or --score); the record\'s '
                   'output is None.  With --fused-decode the float output is not even allocated (outputs=False)')
@@ -927,6 +949,10 @@ def main(argv=None):
     if not 1 <= args.curve_steps <= 16:
       ap.error('--curve-steps must be in 1..16')
     cfg.curve_steps = args.curve_steps
+  if args.fused_decode_curves and args.stepwise:
+    ap.error('--fused-decode-curves does not go with --stepwise: the pass from codes is the fused one')
+  if args.fused_decode_curves:
+    args.fused_decode = args.fused_curves = True
   if args.fused_curves and args.stepwise:
     ap.error('--fused-curves does not go with --stepwise: they are two schedules of the full-resolution pass')
   agent = Agent(cfg).to(dev)
@@ -947,11 +973,13 @@ def main(argv=None):
   if args.score:
     args.device_png = True
   if args.fused_decode:
-    if any(f.uses_generic_kernels() for f in agent.filters):
-      ap.error('--fused-decode needs 8-step curves: there is no pass from codes for --curve-steps %d' % cfg.curve_steps)
+    if any(f.uses_generic_kernels() for f in agent.filters) and not args.fused_decode_curves:
+      ap.error('--fused-decode needs 8-step curves: the pass from codes for --curve-steps %d is '
+               '--fused-decode-curves' % cfg.curve_steps)
     if args.stepwise or args.masking or ((args.show_input or args.show_linear) and not args.device_input_png):
-      ap.error('--fused-decode does not go with --stepwise, --masking or --show-input: the pass from codes is the '
-               'unmasked fused one, and the tone-mapped picture needs the float input')
+      ap.error('%s does not go with --stepwise, --masking or --show-input: the pass from codes is the unmasked fused '
+               'one, and the tone-mapped picture needs the float input'
+               % ('--fused-decode-curves' if args.fused_decode_curves else '--fused-decode'))
     args.device_decode = args.device_proxy = True
   if args.device_input_png:
     args.device_decode = True
@@ -1045,7 +1073,7 @@ def main(argv=None):
       raws = [load_raw(path) for path in paths]
       staged = list(stage_raws(raws, dt, dev))  # the codes go up once, for the pass and for the input pictures
       res = retouch_batch_raw(agent, raws, dt, dev, return_trace='full', intermediates=inter_kind, picture=picture,
-                              outputs=not args.pictures_only, staged=staged)
+                              outputs=not args.pictures_only, staged=staged, curves=curves)
       # emit reads of `hi` its size alone here (the input pictures come from the codes): the codes have it
       emit_batch(paths, [codes[None] for codes, _kind in raws], res, input_pictures(raws, staged))
   elif args.batch == 1 or args.stepwise:

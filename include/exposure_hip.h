@@ -59,7 +59,8 @@ extern "C" {
                               expo_patch_stats, expo_stat_hist, expo_chain_fused_masked_fwd_ragged,
                               expo_decode_tables, expo_bilinear_resize_ragged_codes,
                               expo_chain_fused_fwd_ragged_codes, expo_codes_max_ragged,
-                              expo_codes_lut_ragged, expo_chain_fused_curves_fwd_ragged */
+                              expo_codes_lut_ragged, expo_chain_fused_curves_fwd_ragged,
+                              expo_chain_fused_curves_fwd_ragged_codes */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -403,6 +404,31 @@ int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* p
 int expo_chain_fused_curves_fwd_ragged(const int32_t* filter_ids, const float* params, int steps, int curve_steps,
                                        const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                        int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream);
+
+/*
+ * The fused inference pass for any cfg.curve_steps straight from the integer codes: an added export of ABI 9 (the
+ * version is unchanged).  It replaces expo_decode_ragged followed by expo_chain_fused_curves_fwd_ragged -- and with them
+ * the decoded float input, which is never written or re-read -- as expo_chain_fused_fwd_ragged_codes replaces
+ * expo_decode_ragged + expo_chain_fused_fwd_ragged_taps for L = 8.  Every result is bit-identical to that pair.
+ *   filter_ids, params, steps, curve_steps        as expo_chain_fused_curves_fwd_ragged: params is device float32
+ *                                                 [n][steps][EXPO_MAX_PARAMS_CURVES], curve_steps = L one value per call
+ *   codes, channels, code_bits, tables, table_stride   as expo_chain_fused_fwd_ragged_codes (below): image i's input is
+ *                                                 codes[i] plus its table at entry i * table_stride, in `dtype`; a
+ *                                                 pixel value enters the step loop as float(cast table value)
+ *   ys, hs, ws, n, dtype, tap_mask, tap_format, taps   as both: tap_mask == 0 is allowed (taps may be NULL), ys NULL is
+ *                                                 allowed with taps, ys NULL with tap_mask == 0 is EXPO_E_BADARG
+ * 64 images per launch by value in the kernel arguments, more as further launches on `stream`; per image the vector path
+ * under the rule of expo_chain_fused_fwd_ragged_codes; the cache policy from the call's total bytes.  Validated before
+ * anything is enqueued (EXPO_E_BADARG / EXPO_E_BADDTYPE), the union of the two: curve_steps in [1, EXPO_CURVE_MAX_STEPS],
+ * channels 1, 3 or 4, code_bits 8 or 16, table_stride 0 or >= 2^code_bits, tables non-NULL and 4-byte aligned, steps in
+ * [0, 64], the taps' arguments, no null pointer and no null per-image pointer, the codes of one image smaller than
+ * 2 GiB; n == 0 is a no-op.  No backward, no spatial masks.
+ */
+int expo_chain_fused_curves_fwd_ragged_codes(const int32_t* filter_ids, const float* params, int steps, int curve_steps,
+                                             const void* const* codes, int channels, int code_bits, const void* tables,
+                                             int table_stride, void* const* ys, const int* hs, const int* ws, int n,
+                                             int dtype, uint64_t tap_mask, int tap_format, void* const* taps,
+                                             void* stream);
 
 /*
  * Decode: the integer codes of n input images, as the file holds them, to the linear storage tensors that
