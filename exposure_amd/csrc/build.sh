@@ -1,10 +1,12 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
 # Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
-# chain_fused_curves_codes.hip, the eighteenth; extra arguments go to every compile step.
+# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth; extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
+#   chain_steps_bwd.hip  runs of element-wise backward steps of expo_chain_bwd in one launch (the flags of
+#                        exposure_hip.hip: it must reproduce the per-step kernels bit for bit)
 #   chain_fused.hip      the VALU-bound fused inference kernel (-fno-slp-vectorize -fno-honor-nans, see the file)
 #   chain_fused_codes.hip  the fused inference pass reading the files' integer codes (exactly chain_fused.hip's flags:
 #                        it includes that file for the step loop and the stores and must reproduce its outputs bit for bit)
@@ -76,6 +78,8 @@ p16=$!
 p17=$!
 "$HIPCC" "${FLAGS[@]}" -fno-slp-vectorize -fno-honor-nans "$@" -c "$HERE/chain_fused_curves_codes.hip" -o "$TMP/chain_fused_curves_codes.o" &
 p18=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps_bwd.hip" -o "$TMP/chain_steps_bwd.o" &
+p19=$!
 wait $p1
 wait $p2
 wait $p3
@@ -94,5 +98,6 @@ wait $p15
 wait $p16
 wait $p17
 wait $p18
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" -o "$OUT"
+wait $p19
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

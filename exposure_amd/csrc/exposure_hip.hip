@@ -1913,6 +1913,17 @@ static int chain_fuse_steps(const ChainPlan& plan) {
   return k < kChainFuseMax ? k : kChainFuseMax;
 }
 
+// How many consecutive ELEMENT-WISE backward steps of a chunk go into one launch (chain_steps_bwd.hip: the gradient
+// stays in registers from step to step, every intermediate grads[i] is still stored, the re-read of what the previous
+// launch wrote is gone).  EXPO_CHAIN_FUSE_BWD_STEPS=<k> forces the maximum (1: one kernel per step, the launches before
+// the fused kernel existed).  The reversed walk alternates the direction launch by launch: one launch per step.
+static int chain_fuse_bwd_steps(const ChainPlan& plan) {
+  static const int forced = env_int("EXPO_CHAIN_FUSE_BWD_STEPS", 0);
+  if (plan.snake) return 1;
+  const int k = forced > 0 ? forced : kChainFuseMax;
+  return k < kChainFuseMax ? k : kChainFuseMax;
+}
+
 extern "C" {
 
 int expo_version(void) { return EXPO_ABI_VERSION; }
@@ -2260,11 +2271,38 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts, void* co
     if (int rc = chain_fork(fj, s)) return rc;
   }
   int rc = EXPO_OK;
+  // runs of up to `fuse` consecutive steps of the run table (chain_steps_bwd_fusable) that store their dx go into one launch each
+  // (chain_steps_bwd.hip); off the dwordx3 vector path -- the activations' test plus the same alignment of every
+  // gradient -- every step keeps its own kernel, decided here once for the whole call
+  int fuse = chain_steps_vec_path(acts, steps - 1, h, w, dtype) ? chain_fuse_bwd_steps(plan) : 1;
+  for (int i = 0; i <= steps && fuse > 1; ++i)
+    if ((reinterpret_cast<uintptr_t>(grads[i]) & 3) != 0) fuse = 1;
+  // the steps i, i - 1, .. that one launch takes: a run ends at a step outside the table (Tone / Color, Contrast,
+  // WNB), at a step without a dx (step 0 when
+  // grads[0] is NULL keeps its HAS_DX = false kernel), at `fuse` steps and where the run's accumulators fill their LDS
+  auto run_from = [&](int i) {
+    int cnt = 0, acc_floats = 0;
+    while (cnt < fuse && i - cnt >= 0) {
+      const int id = filter_ids[i - cnt];
+      if (!chain_steps_bwd_fusable(id, dtype, hsv_grad_mode) || !grads[i - cnt]) break;
+      acc_floats += chain_steps_bwd_acc_floats(id);
+      if (acc_floats > kChainBwdAccFloatsMax) break;
+      ++cnt;
+    }
+    return cnt > 1 ? cnt : 1;
+  };
   for (size_t c = 0; c < plan.chunks.size() && !rc; ++c) {
     const ChainChunk& ck = plan.chunks[c];
     hipStream_t sp = ck.lane ? fj->helper : s;
     const size_t ioff = size_t(ck.nb) * h * w * 3 * esz;
-    for (int i = steps - 1; i >= 0 && !rc; --i) {
+    int cnt = 1;
+    for (int i = steps - 1; i >= 0 && !rc; i -= cnt) {
+      cnt = fuse > 1 ? run_from(i) : 1;
+      if (cnt > 1) {
+        rc = chain_steps_bwd(filter_ids, i, cnt, acts, grads, params, records, step_floats, ck.nb, ck.np, h, w, dtype,
+                             hsv_grad_mode, n, sp);
+        continue;
+      }
       // the forward launch of step steps-1 walked in direction (steps-1) & 1 and ENDED on the other side: the backward
       // starts there, i.e. walks the opposite way, and alternates down to step 0, whose direction (1) is again the
       // opposite of the next forward call's first launch (0).  (Until r04p22 this read (steps - i) & 1, which is the

@@ -118,6 +118,19 @@ constexpr int kChainFuseMax = 8;
 bool chain_steps_vec_path(void* const* acts, int steps, int h, int w, int dtype);
 int chain_steps_fwd(const int* ids, int cnt, void* const* acts, const float* const* params, int nb, int np, int h,
                     int w, int dtype, int n_geom, hipStream_t s);
+// defined in chain_steps_bwd.hip, used by expo_chain_bwd.  chain_steps_bwd enqueues steps i0, i0 - 1, .., i0 - cnt + 1
+// (2 <= cnt <= kChainFuseMax, every one chain_steps_bwd_fusable -- the element-wise filters whose fused body gives the
+// per-step kernel's bits: ids 0, 1, 2, 3, 8, without S+ in fp32 with hsv_grad_mode 1 -- and with a grads[i]) of the
+// chain's ids / acts / grads / params on images [nb, nb + np) as ONE launch with filter_bwd_kernel's kGeomReduce
+// geometry of a batch of n_geom images; step i's records go to records + i * step_floats as a per-step launch's would.
+// The kernel keeps a run's accumulators in LDS: chain_steps_bwd_acc_floats(id) floats per thread for a step, at most
+// kChainBwdAccFloatsMax (48 KiB per block) for a run.
+constexpr int kChainBwdAccFloatsMax = 48;
+int chain_steps_bwd_acc_floats(int id);
+bool chain_steps_bwd_fusable(int id, int dtype, int mode);
+int chain_steps_bwd(const int* ids, int i0, int cnt, void* const* acts, void* const* grads,
+                    const float* const* params, float* records, size_t step_floats, int nb, int np, int h, int w,
+                    int dtype, int mode, int n_geom, hipStream_t s);
 
 inline int check_common(int n, int h, int w, int dtype) {
   if (n < 0 || h < 1 || w < 1) return fail(EXPO_E_BADARG, "n >= 0, h >= 1, w >= 1 required");
