@@ -114,6 +114,11 @@ SIGNATURES = {
                                    _vp]),
     'expo_codes_lut_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i, _vp, _i, _i,
                                    ctypes.POINTER(_vp), _vp]),
+    'expo_png_segment_bytes': (_i, []),
+    'expo_png_encode_bound': (ctypes.c_int64, [_i, _i]),
+    'expo_png_encode_workspace_bytes': (_sz, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    'expo_png_encode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp),
+                                    ctypes.POINTER(ctypes.c_int64), _vp, _vp, _sz, _vp]),
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -1035,6 +1040,73 @@ def codes_lut_ragged(codes, luts, stride, outs):
     _check(lib.expo_codes_lut_ragged(_ptr_array(codes), (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), n, c, bits,
                                      _ptr(luts), stride, _CODE_BITS[ot], _ptr_array(outs), _stream()),
            'expo_codes_lut_ragged')
+
+
+PNG_FILTERS = ('none', 'sub', 'up', 'average', 'paeth', 'adaptive')  # expo_png_encode_ragged's filter 0..5
+
+
+def png_segment_bytes():
+  """``expo_png_segment_bytes``: the stream bytes of one deflate segment."""
+  return int(load().expo_png_segment_bytes())
+
+
+def png_encode_bound(h, w):
+  """``expo_png_encode_bound``: the largest file of an (h, w, 3) picture, 75 + 17 ceil(S / SEG) + S, S = h (1 + 3 w)."""
+  bound = int(load().expo_png_encode_bound(int(h), int(w)))
+  if bound < 0:
+    _check(-1, 'expo_png_encode_bound')  # EXPO_E_BADARG, with the library's message
+  return bound
+
+
+def png_encode_ragged(pictures, filter='adaptive', outs=None, workspace=None):
+  """``expo_png_encode_ragged``: 8-bit RGB PNG files of N pictures, made on the device -> (outs, sizes).  pictures: N
+  contiguous (H_i, W_i, 3) uint8 tensors on one ROCm device; filter: a name of ``PNG_FILTERS`` or its number 0..5; outs:
+  N contiguous uint8 device tensors of at least ``png_encode_bound(H_i, W_i)`` bytes (allocated when None); file i is
+  ``outs[i][:sizes[i]]`` with sizes an int64 device tensor (N,).  Nothing is downloaded and the host is not waited for.
+  The shared workspace serves the call unless ``workspace=`` is given."""
+  lib = load()
+  n = len(pictures)
+  if isinstance(filter, str):
+    if filter not in PNG_FILTERS:
+      raise ExposureHipError('exposure_amd: filter must be one of %s, got %r' % (', '.join(PNG_FILTERS), filter))
+    filter = PNG_FILTERS.index(filter)
+  filter = int(filter)
+  if not 0 <= filter <= 5:
+    raise ExposureHipError('exposure_amd: filter must be in 0..5, got %d' % filter)
+  if outs is not None and len(outs) != n:
+    raise ExposureHipError('exposure_amd: pictures and outs must have the same length')
+  if n == 0:
+    return [], None
+  if not isinstance(pictures[0], torch.Tensor) or not pictures[0].is_cuda:
+    raise ExposureHipError('exposure_amd: pictures must be tensors on a ROCm device (HIP path only, no CPU fallback)')
+  device = pictures[0].device
+  for i, p in enumerate(pictures):
+    if not isinstance(p, torch.Tensor) or p.dtype is not torch.uint8 or p.dim() != 3 or p.shape[2] != 3 or \
+        p.device != device or not p.is_contiguous() or p.numel() == 0:
+      raise ExposureHipError('exposure_amd: pictures[%d] must be a contiguous (H, W, 3) uint8 tensor on %s' % (i, device))
+  hs, ws = [int(p.shape[0]) for p in pictures], [int(p.shape[1]) for p in pictures]
+  bounds = [png_encode_bound(h, w) for h, w in zip(hs, ws)]
+  if outs is None:
+    outs = [torch.empty((b,), dtype=torch.uint8, device=device) for b in bounds]
+  for i, o in enumerate(outs):
+    if not isinstance(o, torch.Tensor) or o.dtype is not torch.uint8 or o.device != device or not o.is_contiguous() or \
+        o.numel() < bounds[i]:
+      raise ExposureHipError('exposure_amd: outs[%d] must be a contiguous uint8 tensor of at least %d bytes on %s'
+                             % (i, bounds[i], device))
+  sizes = torch.empty((n,), dtype=torch.int64, device=device)
+  hsa, wsa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws)
+  caps = (ctypes.c_int64 * n)(*[o.numel() for o in outs])
+  with torch.cuda.device(device):
+    need = int(lib.expo_png_encode_workspace_bytes(hsa, wsa, n))
+    if workspace is None:
+      workspace = reserve_workspace(device, need)
+      _order_shared_workspace(device)
+    if not workspace.is_cuda or workspace.device != device or workspace.numel() * workspace.element_size() < need:
+      raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' % (need, device))
+    _check(lib.expo_png_encode_ragged(_ptr_array(pictures), hsa, wsa, n, filter, _ptr_array(outs), caps, _ptr(sizes),
+                                      _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+           'expo_png_encode_ragged')
+  return outs, sizes
 
 
 def area_resize_ragged(xs, windows, S, out):

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
 # Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
-# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth; extra arguments go to every compile step.
+# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth;
+# extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
 #                        must reproduce the per-step kernels bit for bit)
@@ -32,6 +33,9 @@
 #   chain_fused_curves_codes.hip  the fused inference pass for any cfg.curve_steps reading the files' integer codes
 #                        (exactly chain_fused.hip's flags: the step loop of chain_fused_curves.hip behind the loader of
 #                        chain_fused_codes.hip, bit for bit decode + that pass)
+#   png_encode.hip      8-bit PNG files made on the device: the row filter and a Huffman-only deflate in independent
+#                        segments (default flags: integer code; png_deflate.h holds its serial routines, which
+#                        tools/png_rehearse.cpp runs on the host)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -80,6 +84,8 @@ p17=$!
 p18=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps_bwd.hip" -o "$TMP/chain_steps_bwd.o" &
 p19=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/png_encode.hip" -o "$TMP/png_encode.o" &
+p20=$!
 wait $p1
 wait $p2
 wait $p3
@@ -99,5 +105,6 @@ wait $p16
 wait $p17
 wait $p18
 wait $p19
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" -o "$OUT"
+wait $p20
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

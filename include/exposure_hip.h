@@ -60,7 +60,8 @@ extern "C" {
                               expo_decode_tables, expo_bilinear_resize_ragged_codes,
                               expo_chain_fused_fwd_ragged_codes, expo_codes_max_ragged,
                               expo_codes_lut_ragged, expo_chain_fused_curves_fwd_ragged,
-                              expo_chain_fused_curves_fwd_ragged_codes */
+                              expo_chain_fused_curves_fwd_ragged_codes, expo_png_segment_bytes,
+                              expo_png_encode_bound, expo_png_encode_workspace_bytes, expo_png_encode_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -527,6 +528,46 @@ int expo_codes_max_ragged(const void* const* codes, const int* hs, const int* ws
                           int32_t* maxima, void* workspace, size_t workspace_bytes, void* stream);
 int expo_codes_lut_ragged(const void* const* codes, const int* hs, const int* ws, int n, int channels, int code_bits,
                           const void* luts, int lut_stride, int out_bits, void* const* outs, void* stream);
+
+/*
+ * 8-bit PNG files made on the device (png_encode.hip): the file show_and_save writes with cv2.imwrite
+ * (net.py:769-772), without a host compressor.  Added exports of ABI 9 (the version is unchanged).
+ *
+ * The file: signature; IHDR (bit depth 8, colour type 2, no interlace); one IDAT with the zlib header 78 01; one IDAT
+ * per segment of SEG bytes of the filtered stream (row r: one type byte, then its 3 w filtered bytes, bpp = 3); one
+ * IDAT with the stream's Adler-32; IEND.  A segment is deflated on its own and ends on a byte boundary: one dynamic
+ * Huffman block of literals only (HLIT 0, HDIST 0 with the unused distance code of length 1, HCLEN 15 with the fixed
+ * code-length code "0..15 have length 4", so a header of 1106 bits; lengths from a Huffman construction over the
+ * segment's bytes and one end-of-block, limited to 15 bits, canonical codes), followed by an empty stored block (zlib's
+ * sync flush) unless it is the last, which sets BFINAL; or one stored block, exactly when the dynamic form is not
+ * smaller.  No LZ77 matches.  The bytes depend on the picture and `filter` alone.
+ *
+ * expo_png_segment_bytes (net.py:769-772): SEG, a compile-time constant, 16384 <= SEG <= 65535.
+ * expo_png_encode_bound (net.py:769-772): the largest file of an h x w picture, 75 + 17 ceil(S / SEG) + S with
+ *   S = h (1 + 3 w); reached exactly by incompressible pictures.  -1 (with a message) when h or w is below 1 or
+ *   S >= 2^31.
+ * expo_png_encode_workspace_bytes (net.py:769-772): the scratch a call on these n pictures needs (0 for invalid
+ *   arguments): per picture of a launch group its row types, a slot of SEG + 32 bytes and 24 bytes per segment.
+ * expo_png_encode_ragged (net.py:769-772):
+ *   pics         HOST array of n device pointers, picture i is contiguous [hs[i]][ws[i]][3] uint8, any alignment.
+ *   filter       0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth for every row; 5 adaptive: per row the type with the smallest
+ *                sum of min(b, 256 - b) over its filtered bytes (libpng's heuristic), ties to the lowest type.
+ *   outs         HOST array of n device pointers to byte buffers, any alignment; out_capacity HOST [n], each at least
+ *                expo_png_encode_bound(hs[i], ws[i]).  File i is outs[i][0 .. sizes[i]).
+ *   sizes        DEVICE int64 [n]: the files' lengths.
+ *   workspace    caller-owned, 16-byte aligned device scratch of at least expo_png_encode_workspace_bytes(...) bytes;
+ *                needs no initialisation and carries no state.
+ * Allocates nothing, does not synchronise with the host, can be captured.  64 pictures per launch group (four launches,
+ * three with a fixed filter), more as further groups on `stream`.  Everything is validated before anything is enqueued
+ * (EXPO_E_BADARG: n < 0, filter outside 0..5, h or w below 1, S >= 2^31, a capacity below the bound, a workspace that
+ * is too small, null pointers); n == 0 is a no-op.
+ */
+int expo_png_segment_bytes(void);
+int64_t expo_png_encode_bound(int h, int w);
+size_t expo_png_encode_workspace_bytes(const int* hs, const int* ws, int n);
+int expo_png_encode_ragged(const void* const* pics, const int* hs, const int* ws, int n, int filter, void* const* outs,
+                           const int64_t* out_capacity, int64_t* sizes, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /*
  * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of
