@@ -1924,6 +1924,19 @@ static int chain_fuse_bwd_steps(const ChainPlan& plan) {
   return k < kChainFuseMax ? k : kChainFuseMax;
 }
 
+// Does a run of the backward recompute its interior activations from the run's lowest one (chain_steps_bwd_rc.hip: c + 2
+// passes for c steps instead of 2 c + 1) or load them all (chain_steps_bwd.hip)?  Recomputing relies on acts[i + 1] being
+// step i's forward of acts[i] (include/exposure_hip.h at expo_chain_bwd); EXPO_CHAIN_BWD_RECOMPUTE=0, read once per
+// process, enqueues the loading kernels for a caller that edits activations between expo_chain_fwd and expo_chain_bwd.
+static bool chain_bwd_recompute() {
+  // (env_int takes only positive values: "0" is the setting that matters here)
+  static const bool on = [] {
+    const char* v = getenv("EXPO_CHAIN_BWD_RECOMPUTE");
+    return !v || !*v || atoi(v) != 0;
+  }();
+  return on;
+}
+
 extern "C" {
 
 int expo_version(void) { return EXPO_ABI_VERSION; }
@@ -2291,6 +2304,7 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts, void* co
     }
     return cnt > 1 ? cnt : 1;
   };
+  const bool recompute = chain_bwd_recompute();  // (a run's launch, not how runs are collected)
   for (size_t c = 0; c < plan.chunks.size() && !rc; ++c) {
     const ChainChunk& ck = plan.chunks[c];
     hipStream_t sp = ck.lane ? fj->helper : s;
@@ -2299,8 +2313,9 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts, void* co
     for (int i = steps - 1; i >= 0 && !rc; i -= cnt) {
       cnt = fuse > 1 ? run_from(i) : 1;
       if (cnt > 1) {
-        rc = chain_steps_bwd(filter_ids, i, cnt, acts, grads, params, records, step_floats, ck.nb, ck.np, h, w, dtype,
-                             hsv_grad_mode, n, sp);
+        rc = (recompute ? chain_steps_bwd_rc : chain_steps_bwd)(filter_ids, i, cnt, acts, grads, params, records,
+                                                                 step_floats, ck.nb, ck.np, h, w, dtype, hsv_grad_mode,
+                                                                 n, sp);
         continue;
       }
       // the forward launch of step steps-1 walked in direction (steps-1) & 1 and ENDED on the other side: the backward

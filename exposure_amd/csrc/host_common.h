@@ -131,6 +131,14 @@ bool chain_steps_bwd_fusable(int id, int dtype, int mode);
 int chain_steps_bwd(const int* ids, int i0, int cnt, void* const* acts, void* const* grads,
                     const float* const* params, float* records, size_t step_floats, int nb, int np, int h, int w,
                     int dtype, int mode, int n_geom, hipStream_t s);
+// defined in chain_steps_bwd_rc.hip, used by expo_chain_bwd: chain_steps_bwd with the same arguments, launches and
+// results, but the kernel loads only acts[i0 - cnt + 1] and recomputes acts[i0 - cnt + 2 .. i0] from it in registers
+// (where chain_steps_bwd_recomputes(id of the step below, dtype); otherwise it keeps that load).  It relies on
+// acts[i + 1] being step i's forward of acts[i] -- the contract at expo_chain_bwd in include/exposure_hip.h.
+bool chain_steps_bwd_recomputes(int id, int dtype);
+int chain_steps_bwd_rc(const int* ids, int i0, int cnt, void* const* acts, void* const* grads,
+                       const float* const* params, float* records, size_t step_floats, int nb, int np, int h, int w,
+                       int dtype, int mode, int n_geom, hipStream_t s);
 
 inline int check_common(int n, int h, int w, int dtype) {
   if (n < 0 || h < 1 || w < 1) return fail(EXPO_E_BADARG, "n >= 0, h >= 1, w >= 1 required");

@@ -294,6 +294,13 @@ int expo_chain_fwd(const int* filter_ids, int steps, void* const* acts,
  *   dparams  host array of `steps` device pointers, float32 [N][P_i], overwritten.
  *   workspace_bytes >= steps * expo_workspace_bytes(n, h, w, dtype): every step keeps its block
  *   records until the ONE finish launch at the end of the chain has produced all dparams.
+ *   acts     must be what the forward made: acts[i + 1] = filter filter_ids[i] with params[i] applied to
+ *            acts[i], as expo_chain_fwd (or expo_filter_fwd step by step) leaves them.  Consecutive
+ *            element-wise steps run as one launch that loads only the LOWEST step's activation and
+ *            recomputes the ones above it in registers, bit for bit, so the interior
+ *            acts[i] of such a run are NOT read.  A caller that edits activations between the forward
+ *            and the backward sets EXPO_CHAIN_BWD_RECOMPUTE=0 in the environment (read once per
+ *            process): every step then reads its acts[i], with the same results for unedited ones.
  */
 int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts,
                    void* const* grads, const float* const* params,
