@@ -77,8 +77,10 @@ __device__ __forceinline__ void run_reduce(const float* lds, float* rec) {
 // contracts them one way in filter_bwd_kernel (whose accumulators are loop-carried registers that the SLP vectoriser
 // pairs, taking the sums with them) and the other way here: WNB's dparams differ in the last bits in both storage
 // types, Contrast's dparams in fp16 and dparams and dx in fp32.  Exposure, Gamma, White balance, S+ and Level give the
-// per-step bits at every run length, in both storage types and cache policies -- except S+ with hsv_grad_mode 1 in
-// fp32 (its dx differs in 0.4 % of the values), which chain_steps_bwd_fusable keeps out as well.
+// per-step bits at every run length 2..8, for every ordered pair of neighbouring filters, in both storage types and
+// cache policies and in both run kernels (tests/test_hip_chain_bwd_pairs.py holds them to that, clamp edges and
+// saturating values included) -- except S+ with hsv_grad_mode 1 in fp32 (its dx differs in 0.4 % of the values),
+// which chain_steps_bwd_fusable keeps out as well.
 #define EXPO_RUN_FILTERS(X) X(0, ExposureF) X(1, GammaF) X(2, WhiteBalanceF) X(3, SatPlusF) X(8, LevelF)
 
 }  // namespace expo

@@ -20,7 +20,9 @@
 // before anything is stored; activations are never written here.
 //
 // Which forwards are recomputed is a static table per (filter id, storage type), EXPO_RC_FILTERS below, decided by the
-// GPU comparison like EXPO_RUN_FILTERS.  Where a step's forward is not in it, the step above keeps loading its x from
+// GPU comparison like EXPO_RUN_FILTERS: tests/test_hip_chain_bwd_pairs.py runs every ordered pair of the table's
+// filters inside a run, every run length 2..8, both storage types, both modes and both cache policies against the
+// per-step kernels, on images that hold the filters' clamp edges and values that saturate the fp16 store.  Where a step's forward is not in it, the step above keeps loading its x from
 // acts (issued up front with the pair) and the sweep restarts from that loaded value: L such loads make L + 1 + c
 // passes.
 //
