@@ -22,6 +22,7 @@
 #include "pixel_io.h"
 #include "kernel_common.h"
 #include "host_common.h"
+#include "ragged_launch.h"
 
 #ifndef EXPO_FUSED_MIN_WAVES
 #define EXPO_FUSED_MIN_WAVES  // e.g. -DEXPO_FUSED_MIN_WAVES=,8 : register budget for 8 waves per SIMD (probe builds)
@@ -202,10 +203,10 @@ __global__ __launch_bounds__(kThreads EXPO_FUSED_MIN_WAVES) void chain_fused_fwd
 // The chain is per pixel: an image matters to it through its base address and pixel count only.  The grid is 1-D
 // over the images' blocks laid end to end (image i: ceil(groups_i / kThreads) blocks, one chunk per wave as above);
 // the table of up to kRaggedMaxImages images travels BY VALUE in the kernel arguments (no library-owned device
-// memory, no copy; 1.6 KB of the 4 KB kernarg block), a call with more images is split into launches of that many.
-// A block finds its image by a binary search over `first` with the block index -- uniform, so the search, the
-// image's pointers, its pixel count and its ids / params row are all scalar.
-constexpr int kRaggedMaxImages = 64;
+// memory, no copy; 1.6 KB of the 4 KB kernarg block).  A block finds its image by a binary search over `first` with the
+// block index -- uniform, so the search, the image's pointers, its pixel count and its ids / params row are all scalar.
+// The host side -- the checks of a call, its split into launches, the tables' first / n / vec and the choice among
+// (IoStream | IoCached) x ANY_SLOW -- is ragged_launch.h's for every ragged pass; DESIGN.md §3.31 states its contract.
 template <typename T>
 struct RaggedTable {
   const T* x[kRaggedMaxImages];
@@ -499,49 +500,30 @@ static int chain_fused_fwd_t(const int32_t* ids, const float* params, int steps,
   return EXPO_OK;
 }
 
-// arguments validated by the caller; launches of up to kRaggedMaxImages images each, in order, on stream s
+// ragged_launches' `fill` (ragged_launch.h) for the plain table; ys NULL = no image output
+template <typename T>
+static auto ragged_fill(const void* const* xs, void* const* ys, const int* hs, const int* ws) {
+  return [=](RaggedTable<T>& tab, int j, int i) {
+    tab.x[j] = static_cast<const T*>(xs[i]);
+    tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+    tab.hw[j] = hs[i] * ws[i];
+    return ragged_addr(xs[i]) | ragged_addr(tab.y[j]);
+  };
+}
+
+// arguments validated by the caller; the launches are ragged_launches', in order on stream s
 template <typename T>
 static int chain_fused_fwd_ragged_t(const int32_t* ids, const float* params, int steps, const void* const* xs,
                                     void* const* ys, const int* hs, const int* ws, int n, hipStream_t s) {
-  constexpr int PPL = PixTraits<T>::PPL;
-  // cache policy from the bytes of the whole call (what a single tensor of the same pixels would choose)
-  long bytes = 0;
-  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
-  const bool stream = bytes >= stream_min_bytes();
-  for (int base = 0; base < n; base += kRaggedMaxImages) {
-    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
-    RaggedTable<T> tab = {};
-    tab.n = m;
-    bool any_slow = false;
-    long blocks = 0;
-    for (int j = 0; j < m; ++j) {
-      const int i = base + j, hw = hs[i] * ws[i];
-      tab.x[j] = static_cast<const T*>(xs[i]);
-      tab.y[j] = static_cast<T*>(ys[i]);
-      tab.hw[j] = hw;
-      tab.first[j] = int(blocks);
-      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
-      // as make_geom: whole 12-byte vectors and 4-byte aligned bases
-      const bool vec = hw % VecTraits<T>::PPV == 0 && ((reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(ys[i])) & 3) == 0;
-      if (vec) tab.vec |= uint64_t(1) << j;
-      any_slow = any_slow || !vec;
-    }
-    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
-    tab.first[m] = int(blocks);
-    const int32_t* idb = ids + size_t(base) * steps;
-    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
-    if (stream && any_slow)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoStream, true>), grid, block, 0, s, idb, prb, steps, tab);
-    else if (stream)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoStream, false>), grid, block, 0, s, idb, prb, steps, tab);
-    else if (any_slow)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoCached, true>), grid, block, 0, s, idb, prb, steps, tab);
-    else
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, IoCached, false>), grid, block, 0, s, idb, prb, steps, tab);
-    HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged launch");
-  }
-  return EXPO_OK;
+  return ragged_launches<T, RaggedTable<T>>(
+      hs, ws, n, ragged_fill<T>(xs, ys, hs, ws),
+      [&](auto io, auto any_slow, dim3 grid, int base, const RaggedTable<T>& tab) {
+        hipLaunchKernelGGL((chain_fused_fwd_ragged_kernel<T, decltype(io), decltype(any_slow)::value>), grid,
+                           dim3(kThreads), 0, s, ids + size_t(base) * steps,
+                           params + size_t(base) * steps * EXPO_MAX_PARAMS, steps, tab);
+        HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged launch");
+        return EXPO_OK;
+      });
 }
 
 // arguments validated by the caller; tap_mask != 0
@@ -566,52 +548,30 @@ static int chain_fused_fwd_taps_t(const int32_t* ids, const float* params, int s
   return EXPO_OK;
 }
 
+// the same with a tap buffer per image.  A storage tap plane is stored like y (dwordx3), and so is a u16 plane of fp16
+// storage: its base joins the alignment test (tap_vector_store); u8 planes and the u16 planes of fp32 storage take any.
+template <typename T, int FMT>
+static auto ragged_taps_fill(const void* const* xs, void* const* ys, const int* hs, const int* ws, void* const* taps) {
+  return [=](RaggedTapTable<T>& tt, int j, int i) {
+    tt.taps[j] = static_cast<char*>(taps[i]);
+    return ragged_fill<T>(xs, ys, hs, ws)(tt.t, j, i) | (tap_vector_store<T, FMT>() ? ragged_addr(taps[i]) : 0);
+  };
+}
+
 // arguments validated by the caller; tap_mask != 0, ys NULL = no image output
 template <typename T, int FMT>
 static int chain_fused_fwd_ragged_taps_t(const int32_t* ids, const float* params, int steps, const void* const* xs,
                                          void* const* ys, const int* hs, const int* ws, int n, uint64_t tap_mask,
                                          void* const* taps, hipStream_t s) {
-  constexpr int PPL = PixTraits<T>::PPL;
-  long bytes = 0;
-  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
-  const bool stream = bytes >= stream_min_bytes();
-  for (int base = 0; base < n; base += kRaggedMaxImages) {
-    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
-    RaggedTapTable<T> tt = {};
-    RaggedTable<T>& tab = tt.t;
-    tab.n = m;
-    bool any_slow = false;
-    long blocks = 0;
-    for (int j = 0; j < m; ++j) {
-      const int i = base + j, hw = hs[i] * ws[i];
-      tab.x[j] = static_cast<const T*>(xs[i]);
-      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
-      tt.taps[j] = static_cast<char*>(taps[i]);
-      tab.hw[j] = hw;
-      tab.first[j] = int(blocks);
-      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
-      const uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
-                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(taps[i]) : 0);
-      const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
-      if (vec) tab.vec |= uint64_t(1) << j;
-      any_slow = any_slow || !vec;
-    }
-    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
-    tab.first[m] = int(blocks);
-    const int32_t* idb = ids + size_t(base) * steps;
-    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
-    if (stream && any_slow)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoStream, true, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
-    else if (stream)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoStream, false, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
-    else if (any_slow)
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoCached, true, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
-    else
-      hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, IoCached, false, FMT>), grid, block, 0, s, idb, prb, steps, tap_mask, tt);
-    HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged_taps launch");
-  }
-  return EXPO_OK;
+  return ragged_launches<T, RaggedTapTable<T>>(
+      hs, ws, n, ragged_taps_fill<T, FMT>(xs, ys, hs, ws, taps),
+      [&](auto io, auto any_slow, dim3 grid, int base, const RaggedTapTable<T>& tt) {
+        hipLaunchKernelGGL((chain_fused_fwd_ragged_taps_kernel<T, decltype(io), decltype(any_slow)::value, FMT>), grid,
+                           dim3(kThreads), 0, s, ids + size_t(base) * steps,
+                           params + size_t(base) * steps * EXPO_MAX_PARAMS, steps, tap_mask, tt);
+        HIP_TRY(hipGetLastError(), "chain_fused_fwd_ragged_taps launch");
+        return EXPO_OK;
+      });
 }
 
 // kernel arguments of the ragged tap kernel: ids, params, steps, tap_mask, the table
@@ -628,7 +588,6 @@ static_assert(sizeof(RaggedTapTable<half_t>) + 32 <= 4096, "the ragged tap table
 // arithmetic by its ordering anchor) instead of carrying 2 * PPL grid values through the step loop.
 // Mask constants: the six numbers of a step are wave-uniform and are fetched one step ahead, with the id and the
 // parameters; the image's geometry (grid constants, the walk's steps) is set up once per wave in `geo`.
-constexpr int kTapNone = -1;  // FMT of the masked kernels without taps (an EXPO_TAP_* format otherwise)
 struct NoSink { __device__ __forceinline__ void operator()(int, int, int, const float*) const {} };
 
 // `geo` with the coefficients of one step's six mask parameters (MaskPrm::load's own arithmetic; its geometry part
@@ -788,61 +747,35 @@ __global__ __launch_bounds__(kThreads) void chain_fused_masked_ragged_kernel(
   else image(std::false_type());
 }
 
-// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output
+// ragged_launches' `fill` for the masked table; FMT kTapNone: taps unused; ys NULL = no image output
+template <typename T, int FMT>
+static auto masked_fill(const void* const* xs, void* const* ys, const int* hs, const int* ws, void* const* taps) {
+  return [=](MaskedRaggedTable<T>& tab, int j, int i) {
+    tab.x[j] = static_cast<const T*>(xs[i]);
+    tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+    tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
+    tab.h[j] = hs[i];
+    tab.w[j] = ws[i];
+    return ragged_addr(xs[i]) | ragged_addr(tab.y[j]) | (tap_vector_store<T, FMT>() ? ragged_addr(tab.taps[j]) : 0);
+  };
+}
+
+// arguments validated by the caller; FMT kTapNone: tap_mask == 0
 template <typename T, int FMT>
 static int chain_fused_masked_ragged_t(const int32_t* ids, const float* params, const float* mask_params, int steps,
                                        float sharp, float min_strength, const void* const* xs, void* const* ys,
                                        const int* hs, const int* ws, int n, uint64_t tap_mask, void* const* taps,
                                        hipStream_t s) {
-  constexpr int PPL = PixTraits<T>::PPL;
-  long bytes = 0;
-  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
-  const bool stream = bytes >= stream_min_bytes();
-  for (int base = 0; base < n; base += kRaggedMaxImages) {
-    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
-    MaskedRaggedTable<T> tab = {};
-    tab.n = m;
-    bool any_slow = false;
-    long blocks = 0;
-    for (int j = 0; j < m; ++j) {
-      const int i = base + j, hw = hs[i] * ws[i];
-      tab.x[j] = static_cast<const T*>(xs[i]);
-      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
-      tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
-      tab.h[j] = hs[i];
-      tab.w[j] = ws[i];
-      tab.first[j] = int(blocks);
-      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
-      const uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
-                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
-      const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
-      if (vec) tab.vec |= uint64_t(1) << j;
-      any_slow = any_slow || !vec;
-    }
-    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
-    tab.first[m] = int(blocks);
-    const int32_t* idb = ids + size_t(base) * steps;
-    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS;
-    const float* mpb = mask_params + size_t(base) * steps * 6;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
-    if (stream && any_slow)
-      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoStream, true, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
-    else if (stream)
-      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoStream, false, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
-    else if (any_slow)
-      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoCached, true, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
-    else
-      hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, IoCached, false, FMT>), grid, block, 0, s, idb, prb, mpb, steps, sharp, min_strength, tap_mask, tab);
-    HIP_TRY(hipGetLastError(), "chain_fused_masked_fwd_ragged launch");
-  }
-  return EXPO_OK;
-}
-
-static int check_taps(int steps, uint64_t tap_mask, int tap_format) {
-  if (tap_format != EXPO_TAP_STORAGE && tap_format != EXPO_TAP_U8 && tap_format != EXPO_TAP_U16)
-    return fail(EXPO_E_BADARG, "tap_format must be EXPO_TAP_STORAGE, EXPO_TAP_U8 or EXPO_TAP_U16");
-  if (steps < 64 && (tap_mask >> steps) != 0) return fail(EXPO_E_BADARG, "tap_mask has a bit >= steps");
-  return EXPO_OK;
+  return ragged_launches<T, MaskedRaggedTable<T>>(
+      hs, ws, n, masked_fill<T, FMT>(xs, ys, hs, ws, taps),
+      [&](auto io, auto any_slow, dim3 grid, int base, const MaskedRaggedTable<T>& tab) {
+        hipLaunchKernelGGL((chain_fused_masked_ragged_kernel<T, decltype(io), decltype(any_slow)::value, FMT>), grid,
+                           dim3(kThreads), 0, s, ids + size_t(base) * steps,
+                           params + size_t(base) * steps * EXPO_MAX_PARAMS, mask_params + size_t(base) * steps * 6, steps,
+                           sharp, min_strength, tap_mask, tab);
+        HIP_TRY(hipGetLastError(), "chain_fused_masked_fwd_ragged launch");
+        return EXPO_OK;
+      });
 }
 
 }  // namespace expo
@@ -867,16 +800,11 @@ int expo_chain_fused_fwd(const int32_t* filter_ids, const float* params, int ste
 
 int expo_chain_fused_fwd_ragged(const int32_t* filter_ids, const float* params, int steps, const void* const* xs,
                                 void* const* ys, const int* hs, const int* ws, int n, int dtype, void* stream) {
-  // everything is checked before the first launch is enqueued
-  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
-  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
-  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
-  if (n == 0) return EXPO_OK;
-  if (!xs || !ys || !hs || !ws || (steps > 0 && (!filter_ids || !params))) return fail(EXPO_E_BADARG, "null pointer");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
-    if (!xs[i] || !ys[i]) return fail(EXPO_E_BADARG, "null image pointer");
-  }
+  bool go;
+  if (int rc = ragged_check_args(steps, xs, ys, false, hs, ws, n, dtype, 0, EXPO_TAP_STORAGE, nullptr, true,
+                                 filter_ids && params, &go))
+    return rc;
+  if (!go) return EXPO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return dtype == EXPO_F16 ? chain_fused_fwd_ragged_t<half_t>(filter_ids, params, steps, xs, ys, hs, ws, n, s)
                            : chain_fused_fwd_ragged_t<float>(filter_ids, params, steps, xs, ys, hs, ws, n, s);
@@ -892,80 +820,46 @@ int expo_chain_fused_fwd_taps(const int32_t* filter_ids, const float* params, in
   if (n == 0) return EXPO_OK;
   if (!x || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params))) return fail(EXPO_E_BADARG, "null pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool f16 = dtype == EXPO_F16;
-  if (!tap_mask)
-    return f16 ? chain_fused_fwd_t<half_t>(filter_ids, params, steps, x, y, n, h, w, s)
-               : chain_fused_fwd_t<float>(filter_ids, params, steps, x, y, n, h, w, s);
-  if (tap_format == EXPO_TAP_U8)
-    return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_U8>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
-               : chain_fused_fwd_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
-  if (tap_format == EXPO_TAP_U16)
-    return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_U16>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
-               : chain_fused_fwd_taps_t<float, EXPO_TAP_U16>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
-  return f16 ? chain_fused_fwd_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s)
-             : chain_fused_fwd_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
+  return dispatch_dtype_tap(dtype, tap_mask, tap_format, [&](auto t, auto fmt) {
+    using T = decltype(t);
+    constexpr int FMT = decltype(fmt)::value;
+    if constexpr (FMT == kTapNone) return chain_fused_fwd_t<T>(filter_ids, params, steps, x, y, n, h, w, s);
+    else return chain_fused_fwd_taps_t<T, FMT>(filter_ids, params, steps, x, y, n, h, w, tap_mask, taps, s);
+  });
 }
 
 int expo_chain_fused_fwd_ragged_taps(const int32_t* filter_ids, const float* params, int steps,
                                      const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                      int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
-  // everything is checked before the first launch is enqueued
-  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
-  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
-  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
-  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
-  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
-  if (n == 0) return EXPO_OK;
-  if (!xs || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
-    return fail(EXPO_E_BADARG, "null pointer");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
-    if (!xs[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
-    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
-  }
+  bool go;
+  if (int rc = ragged_check_args(steps, xs, ys, true, hs, ws, n, dtype, tap_mask, tap_format, taps, true,
+                                 filter_ids && params, &go))
+    return rc;
+  if (!go) return EXPO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool f16 = dtype == EXPO_F16;
-  if (!tap_mask)
-    return f16 ? chain_fused_fwd_ragged_t<half_t>(filter_ids, params, steps, xs, ys, hs, ws, n, s)
-               : chain_fused_fwd_ragged_t<float>(filter_ids, params, steps, xs, ys, hs, ws, n, s);
-  if (tap_format == EXPO_TAP_U8)
-    return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
-               : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_U8>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
-  if (tap_format == EXPO_TAP_U16)
-    return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_U16>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
-               : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_U16>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
-  return f16 ? chain_fused_fwd_ragged_taps_t<half_t, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s)
-             : chain_fused_fwd_ragged_taps_t<float, EXPO_TAP_STORAGE>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
+  return dispatch_dtype_tap(dtype, tap_mask, tap_format, [&](auto t, auto fmt) {
+    using T = decltype(t);
+    constexpr int FMT = decltype(fmt)::value;
+    if constexpr (FMT == kTapNone) return chain_fused_fwd_ragged_t<T>(filter_ids, params, steps, xs, ys, hs, ws, n, s);
+    else return chain_fused_fwd_ragged_taps_t<T, FMT>(filter_ids, params, steps, xs, ys, hs, ws, n, tap_mask, taps, s);
+  });
 }
 
 int expo_chain_fused_masked_fwd_ragged(const int32_t* filter_ids, const float* params, const float* mask_params,
                                        int steps, float maximum_sharpness, float minimum_strength,
                                        const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                        int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
-  // everything is checked before the first launch is enqueued
-  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
-  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
-  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
-  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
-  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
-  if (n == 0) return EXPO_OK;
-  if (!xs || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params || !mask_params)))
-    return fail(EXPO_E_BADARG, "null pointer");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
-    if (!xs[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
-    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
-  }
+  bool go;
+  if (int rc = ragged_check_args(steps, xs, ys, true, hs, ws, n, dtype, tap_mask, tap_format, taps, true,
+                                 filter_ids && params && mask_params, &go))
+    return rc;
+  if (!go) return EXPO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const float sh = maximum_sharpness, ms = minimum_strength;
-#define EXPO_MASKED(T, FMT) \
-  chain_fused_masked_ragged_t<T, FMT>(filter_ids, params, mask_params, steps, sh, ms, xs, ys, hs, ws, n, tap_mask, taps, s)
-  const bool f16 = dtype == EXPO_F16;
-  if (!tap_mask) return f16 ? EXPO_MASKED(half_t, kTapNone) : EXPO_MASKED(float, kTapNone);
-  if (tap_format == EXPO_TAP_U8) return f16 ? EXPO_MASKED(half_t, EXPO_TAP_U8) : EXPO_MASKED(float, EXPO_TAP_U8);
-  if (tap_format == EXPO_TAP_U16) return f16 ? EXPO_MASKED(half_t, EXPO_TAP_U16) : EXPO_MASKED(float, EXPO_TAP_U16);
-  return f16 ? EXPO_MASKED(half_t, EXPO_TAP_STORAGE) : EXPO_MASKED(float, EXPO_TAP_STORAGE);
-#undef EXPO_MASKED
+  return dispatch_dtype_tap(dtype, tap_mask, tap_format, [&](auto t, auto fmt) {
+    return chain_fused_masked_ragged_t<decltype(t), decltype(fmt)::value>(filter_ids, params, mask_params, steps,
+                                                                          maximum_sharpness, minimum_strength, xs, ys,
+                                                                          hs, ws, n, tap_mask, taps, s);
+  });
 }
 
 }  // extern "C"

@@ -8,7 +8,8 @@
 //
 // A unit of its own, compiled with exactly chain_fused.hip's flags (csrc/build.sh): it includes that file for
 // chain_step, TapSink, the ragged tables and the stores, which it uses untouched, and instantiates none of its kernels
-// (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), so the kernels of chain_fused.hip keep their code and registers.
+// (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), so the kernels of chain_fused.hip keep their code and registers.  The host side
+// of a call is ragged_launch.h's, with chain_fused.hip's fills.
 //   parameters  chain_fused_run keeps two sets of 24 parameters in SGPRs; two sets of 48 do not fit.  The filters that
 //               are no curve read at most three scalars, so only a row's first three entries (and the id) are fetched
 //               one step ahead through scalar loads; a curve step's knots arrive in a lane-mirrored vector load
@@ -116,58 +117,23 @@ __global__ __launch_bounds__(kThreads) void chain_fused_curves_ragged_kernel(
   else image(std::false_type());
 }
 
-// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output.
-// The launches, their split and the vector decision are chain_fused_fwd_ragged_t's / chain_fused_fwd_ragged_taps_t's.
+// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output
 template <typename T, int FMT>
 int chain_fused_curves_ragged_t(const int32_t* ids, const float* params, int steps, int L, const void* const* xs,
                                 void* const* ys, const int* hs, const int* ws, int n, uint64_t tap_mask,
                                 void* const* taps, hipStream_t s) {
-  constexpr int PPL = PixTraits<T>::PPL;
-  long bytes = 0;  // cache policy from the bytes of the whole call
-  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
-  const bool stream = bytes >= stream_min_bytes();
-  for (int base = 0; base < n; base += kRaggedMaxImages) {
-    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
-    CurvesTable<T, FMT> tt = {};
-    RaggedTable<T>& tab = [&]() -> RaggedTable<T>& {
-      if constexpr (FMT == kTapNone) return tt;
-      else return tt.t;
-    }();
-    tab.n = m;
-    bool any_slow = false;
-    long blocks = 0;
-    for (int j = 0; j < m; ++j) {
-      const int i = base + j, hw = hs[i] * ws[i];
-      tab.x[j] = static_cast<const T*>(xs[i]);
-      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
-      uintptr_t a = reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(tab.y[j]);
-      if constexpr (FMT != kTapNone) {
-        tt.taps[j] = static_cast<char*>(taps[i]);
-        if (tap_vector_store<T, FMT>()) a |= reinterpret_cast<uintptr_t>(taps[i]);
-      }
-      tab.hw[j] = hw;
-      tab.first[j] = int(blocks);
-      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
-      const bool vec = hw % VecTraits<T>::PPV == 0 && (a & 3) == 0;
-      if (vec) tab.vec |= uint64_t(1) << j;
-      any_slow = any_slow || !vec;
-    }
-    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
-    tab.first[m] = int(blocks);
-    const int32_t* idb = ids + size_t(base) * steps;
-    const float* prb = params + size_t(base) * steps * EXPO_MAX_PARAMS_CURVES;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
-    if (stream && any_slow)
-      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoStream, true, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
-    else if (stream)
-      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoStream, false, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
-    else if (any_slow)
-      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoCached, true, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
-    else
-      hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, IoCached, false, FMT>), grid, block, 0, s, idb, prb, steps, L, tap_mask, tt);
-    HIP_TRY(hipGetLastError(), "chain_fused_curves_fwd_ragged launch");
-  }
-  return EXPO_OK;
+  const auto fill = [&] {
+    if constexpr (FMT == kTapNone) return ragged_fill<T>(xs, ys, hs, ws);
+    else return ragged_taps_fill<T, FMT>(xs, ys, hs, ws, taps);
+  }();
+  return ragged_launches<T, CurvesTable<T, FMT>>(
+      hs, ws, n, fill, [&](auto io, auto any_slow, dim3 grid, int base, const CurvesTable<T, FMT>& tt) {
+        hipLaunchKernelGGL((chain_fused_curves_ragged_kernel<T, decltype(io), decltype(any_slow)::value, FMT>), grid,
+                           dim3(kThreads), 0, s, ids + size_t(base) * steps,
+                           params + size_t(base) * steps * EXPO_MAX_PARAMS_CURVES, steps, L, tap_mask, tt);
+        HIP_TRY(hipGetLastError(), "chain_fused_curves_fwd_ragged launch");
+        return EXPO_OK;
+      });
 }
 
 // kernel arguments: ids, params, steps, L, tap_mask, the table
@@ -184,32 +150,18 @@ extern "C" {
 int expo_chain_fused_curves_fwd_ragged(const int32_t* filter_ids, const float* params, int steps, int curve_steps,
                                        const void* const* xs, void* const* ys, const int* hs, const int* ws, int n,
                                        int dtype, uint64_t tap_mask, int tap_format, void* const* taps, void* stream) {
-  // everything is checked before the first launch is enqueued
-  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
-  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
-  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
   if (curve_steps < 1 || curve_steps > kCurvesMaxL)
     return fail(EXPO_E_BADARG, "curve_steps must be in [1, EXPO_CURVE_MAX_STEPS]");
-  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
-  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
-  if (n == 0) return EXPO_OK;
-  if (!xs || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
-    return fail(EXPO_E_BADARG, "null pointer");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
-    if (!xs[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
-    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
-  }
+  bool go;
+  if (int rc = ragged_check_args(steps, xs, ys, true, hs, ws, n, dtype, tap_mask, tap_format, taps, true,
+                                 filter_ids && params, &go))
+    return rc;
+  if (!go) return EXPO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = curve_steps;
-#define EXPO_CURVES(T, FMT) \
-  chain_fused_curves_ragged_t<T, FMT>(filter_ids, params, steps, L, xs, ys, hs, ws, n, tap_mask, taps, s)
-  const bool f16 = dtype == EXPO_F16;
-  if (!tap_mask) return f16 ? EXPO_CURVES(half_t, kTapNone) : EXPO_CURVES(float, kTapNone);
-  if (tap_format == EXPO_TAP_U8) return f16 ? EXPO_CURVES(half_t, EXPO_TAP_U8) : EXPO_CURVES(float, EXPO_TAP_U8);
-  if (tap_format == EXPO_TAP_U16) return f16 ? EXPO_CURVES(half_t, EXPO_TAP_U16) : EXPO_CURVES(float, EXPO_TAP_U16);
-  return f16 ? EXPO_CURVES(half_t, EXPO_TAP_STORAGE) : EXPO_CURVES(float, EXPO_TAP_STORAGE);
-#undef EXPO_CURVES
+  return dispatch_dtype_tap(dtype, tap_mask, tap_format, [&](auto t, auto fmt) {
+    return chain_fused_curves_ragged_t<decltype(t), decltype(fmt)::value>(filter_ids, params, steps, curve_steps, xs, ys,
+                                                                          hs, ws, n, tap_mask, taps, s);
+  });
 }
 
 }  // extern "C"

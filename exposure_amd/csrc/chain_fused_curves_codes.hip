@@ -8,8 +8,8 @@
 //
 // A unit of its own, compiled with exactly chain_fused.hip's flags (csrc/build.sh).  Nothing of the device code is its
 // own but the kernel that joins the parts: chain_fused.hip (EXPO_CHAIN_FUSED_TEMPLATES_ONLY) gives chain_step, TapSink
-// and the stores, curves_run.h the step loop and the per-wave curve table, codes_image.h the table of a launch, the
-// loader with its vector and element-wise paths and the split into launches.
+// and the stores, curves_run.h the step loop and the per-wave curve table, codes_image.h the table of a launch and the
+// loader with its vector and element-wise paths; the host side of a call is ragged_launch.h's.
 //   tables      an 8-bit table is staged in LDS once per block; a 16-bit table is read through the caches as ttab[k],
 //               a plain global load -- no pointer or value is pinned into a register by hand anywhere in this unit.
 //   parameters  three scalars and the id per step in SGPRs, the knots through the lane-mirrored vector load
@@ -97,50 +97,33 @@ __global__ __launch_bounds__(kThreads) void chain_fused_fwd_ragged_codes_kernel(
   else image(std::false_type());
 }
 
-// arguments validated by the caller; FMT kTapNone: tap_mask == 0 and taps unused; otherwise ys NULL = no image output
-template <typename CT, int C, typename T, int FMT>
-int chain_fused_curves_codes_t(const int32_t* ids, const float* params, int steps, int L, const void* const* codes,
-                               const void* tables, int table_stride, void* const* ys, const int* hs, const int* ws, int n,
-                               uint64_t tap_mask, void* const* taps, hipStream_t s) {
-  return codes_launches<T, FMT>(
-      ids, params, steps, EXPO_MAX_PARAMS_CURVES, codes, tables, table_stride, ys, hs, ws, n, taps,
-      "chain_fused_curves_fwd_ragged_codes launch",
-      [&](bool stream, dim3 grid, const int32_t* idb, const float* prb, const T* tb, const CodesTable<T>& tab) {
-        const dim3 block(kThreads);
-        if (stream)
-          hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoStream, FMT>), grid, block, 0, s, idb, prb,
-                             steps, L, tap_mask, tb, table_stride, tab);
-        else
-          hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, IoCached, FMT>), grid, block, 0, s, idb, prb,
-                             steps, L, tap_mask, tb, table_stride, tab);
-      });
-}
-
-template <typename CT, int C, typename T>
-int chain_fused_curves_codes_fmt(uint64_t tap_mask, int tap_format, const int32_t* ids, const float* params, int steps,
-                                 int L, const void* const* codes, const void* tables, int table_stride, void* const* ys,
-                                 const int* hs, const int* ws, int n, void* const* taps, hipStream_t s) {
-#define EXPO_CODES(FMT)                                                                                                  \
-  chain_fused_curves_codes_t<CT, C, T, FMT>(ids, params, steps, L, codes, tables, table_stride, ys, hs, ws, n, tap_mask, \
-                                            taps, s)
-  if (!tap_mask) return EXPO_CODES(kTapNone);
-  if (tap_format == EXPO_TAP_U8) return EXPO_CODES(EXPO_TAP_U8);
-  if (tap_format == EXPO_TAP_U16) return EXPO_CODES(EXPO_TAP_U16);
-  return EXPO_CODES(EXPO_TAP_STORAGE);
-#undef EXPO_CODES
-}
-
-template <typename CT, int C, typename... A>
-int chain_fused_curves_codes_dtype(int dtype, A... a) {
-  return dtype == EXPO_F16 ? chain_fused_curves_codes_fmt<CT, C, half_t>(a...)
-                           : chain_fused_curves_codes_fmt<CT, C, float>(a...);
+// arguments validated by the caller; ys NULL = no image output.  The codes kernels hold both paths, so a launch does not
+// look at any_slow.
+template <typename CT, int C>
+int chain_fused_curves_codes_t(int dtype, int tap_format, const int32_t* ids, const float* params, int steps, int L,
+                               const void* const* codes, const void* tables, int table_stride, void* const* ys,
+                               const int* hs, const int* ws, int n, uint64_t tap_mask, void* const* taps, hipStream_t s) {
+  return dispatch_dtype_tap(dtype, tap_mask, tap_format, [&](auto t, auto fmt) {
+    using T = decltype(t);
+    constexpr int FMT = decltype(fmt)::value;
+    return ragged_launches<T, CodesTable<T>>(
+        hs, ws, n, codes_fill<T, FMT>(codes, ys, hs, ws, taps),
+        [&](auto io, auto, dim3 grid, int base, const CodesTable<T>& tab) {
+          hipLaunchKernelGGL((chain_fused_fwd_ragged_codes_kernel<CT, C, T, decltype(io), FMT>), grid, dim3(kThreads),
+                             0, s, ids + size_t(base) * steps, params + size_t(base) * steps * EXPO_MAX_PARAMS_CURVES,
+                             steps, L, tap_mask,
+                             static_cast<const T*>(tables) + size_t(base) * size_t(table_stride), table_stride, tab);
+          HIP_TRY(hipGetLastError(), "chain_fused_curves_fwd_ragged_codes launch");
+          return EXPO_OK;
+        });
+  });
 }
 
 template <typename CT, typename... A>
-int chain_fused_curves_codes_channels(int channels, int dtype, A... a) {
-  if (channels == 1) return chain_fused_curves_codes_dtype<CT, 1>(dtype, a...);
-  if (channels == 3) return chain_fused_curves_codes_dtype<CT, 3>(dtype, a...);
-  return chain_fused_curves_codes_dtype<CT, 4>(dtype, a...);
+int chain_fused_curves_codes_channels(int channels, A... a) {
+  if (channels == 1) return chain_fused_curves_codes_t<CT, 1>(a...);
+  if (channels == 3) return chain_fused_curves_codes_t<CT, 3>(a...);
+  return chain_fused_curves_codes_t<CT, 4>(a...);
 }
 
 }  // namespace
@@ -156,20 +139,20 @@ int expo_chain_fused_curves_fwd_ragged_codes(const int32_t* filter_ids, const fl
                                              int table_stride, void* const* ys, const int* hs, const int* ws, int n,
                                              int dtype, uint64_t tap_mask, int tap_format, void* const* taps,
                                              void* stream) {
-  // everything is checked before the first launch is enqueued
   if (curve_steps < 1 || curve_steps > kCurvesMaxL)
     return fail(EXPO_E_BADARG, "curve_steps must be in [1, EXPO_CURVE_MAX_STEPS]");
+  if (int rc = codes_check_scalars(channels, code_bits, table_stride)) return rc;
   bool go;
-  if (int rc = codes_check_args(filter_ids, params, steps, codes, channels, code_bits, tables, table_stride, ys, hs, ws, n,
-                                dtype, tap_mask, tap_format, taps, &go))
+  if (int rc = ragged_check_args(steps, codes, ys, true, hs, ws, n, dtype, tap_mask, tap_format, taps, tables != nullptr,
+                                 filter_ids && params, &go, codes_check_extra(tables, hs, ws, channels, code_bits)))
     return rc;
   if (!go) return EXPO_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (code_bits == 8)
-    return chain_fused_curves_codes_channels<uint8_t>(channels, dtype, tap_mask, tap_format, filter_ids, params, steps,
-                                                      curve_steps, codes, tables, table_stride, ys, hs, ws, n, taps, s);
-  return chain_fused_curves_codes_channels<uint16_t>(channels, dtype, tap_mask, tap_format, filter_ids, params, steps,
-                                                     curve_steps, codes, tables, table_stride, ys, hs, ws, n, taps, s);
+    return chain_fused_curves_codes_channels<uint8_t>(channels, dtype, tap_format, filter_ids, params, steps, curve_steps,
+                                                      codes, tables, table_stride, ys, hs, ws, n, tap_mask, taps, s);
+  return chain_fused_curves_codes_channels<uint16_t>(channels, dtype, tap_format, filter_ids, params, steps, curve_steps,
+                                                     codes, tables, table_stride, ys, hs, ws, n, tap_mask, taps, s);
 }
 
 }  // extern "C"

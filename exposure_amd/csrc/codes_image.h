@@ -1,13 +1,13 @@
 // codes_image.h -- what the fused ragged passes that read the files' integer codes share (chain_fused_codes.hip,
-// chain_fused_curves_codes.hip): the by-value table of a launch, the loader of one image and the
-// split of a call into launches.  Include it after chain_fused.hip (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), whose PixTraits,
-// stores and ragged constants it uses; the step loop is the including unit's (`run`).
+// chain_fused_curves_codes.hip): the by-value table of a launch with its `fill`, the loader of
+// one image and the codes' own argument checks; the launches are ragged_launch.h's.  Include it after
+// chain_fused.hip (EXPO_CHAIN_FUSED_TEMPLATES_ONLY), whose PixTraits and stores it uses; the step loop is the including
+// unit's (`run`).
 //   vector path       a lane's group keeps pixel_io.h's pixel positions: row r of a wave's chunk is the 12-byte vector
 //                     of PPV pixels (fp16 2, fp32 1) at pixel gw * PPL + r * 64 * PPV + lane * PPV; its PPV * C codes
 //                     come in with the widest buffer load their size allows, as decode_kernel's.  Rows past the end of
 //                     the image read code 0 and their stores are dropped by the bounds checks.
-//   element-wise path per image, block-uniform: codes not 4-byte aligned, hw % PPV != 0, or y / a vector-stored tap
-//                     plane misaligned (the rule of chain_fused.hip with the codes' base added).
+//   element-wise path per image, block-uniform: the vec bit of §3.31 with the codes' base among the addresses.
 #pragma once
 #include "codes_loader.h"
 
@@ -79,73 +79,38 @@ __device__ __forceinline__ void codes_image_loop(const CT* codes, T* yi, int hw,
   }
 }
 
-// The launches of one call (arguments validated by the caller): at most kRaggedMaxImages images each, the cache policy
-// from the bytes of the whole call, as the pass from tensors.  `width` is the floats of a parameter row;
-// launch(stream, grid, ids, params, tables, tab) enqueues one.  FMT kTapNone: taps unused; ys NULL = no image output.
-template <typename T, int FMT, class Launch>
-int codes_launches(const int32_t* ids, const float* params, int steps, int width, const void* const* codes,
-                   const void* tables, int table_stride, void* const* ys, const int* hs, const int* ws, int n,
-                   void* const* taps, const char* what, const Launch& launch) {
-  constexpr int PPL = PixTraits<T>::PPL;
-  long bytes = 0;
-  for (int i = 0; i < n; ++i) bytes += long(hs[i]) * ws[i] * 3L * long(sizeof(T));
-  const bool stream = bytes >= stream_min_bytes();
-  for (int base = 0; base < n; base += kRaggedMaxImages) {
-    const int m = n - base < kRaggedMaxImages ? n - base : kRaggedMaxImages;
-    CodesTable<T> tab = {};
-    tab.n = m;
-    long blocks = 0;
-    for (int j = 0; j < m; ++j) {
-      const int i = base + j, hw = hs[i] * ws[i];
-      tab.codes[j] = codes[i];
-      tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
-      tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
-      tab.hw[j] = hw;
-      tab.first[j] = int(blocks);
-      blocks += ((hw + PPL - 1) / PPL + kThreads - 1) / kThreads;
-      const uintptr_t a = reinterpret_cast<uintptr_t>(codes[i]) | reinterpret_cast<uintptr_t>(tab.y[j]) |
-                          (tap_vector_store<T, FMT>() ? reinterpret_cast<uintptr_t>(tab.taps[j]) : 0);
-      if (hw % VecTraits<T>::PPV == 0 && (a & 3) == 0) tab.vec |= uint64_t(1) << j;
-    }
-    if (blocks > 0x7fffffffL) return fail(EXPO_E_BADARG, "too many blocks in one launch");
-    tab.first[m] = int(blocks);
-    launch(stream, dim3(static_cast<unsigned>(blocks)), ids + size_t(base) * steps,
-           params + size_t(base) * steps * width, static_cast<const T*>(tables) + size_t(base) * size_t(table_stride),
-           tab);
-    HIP_TRY(hipGetLastError(), what);
-  }
-  return EXPO_OK;
+// ragged_launches' `fill` (ragged_launch.h) for a codes pass: the codes' base joins the alignment test.  FMT kTapNone:
+// taps unused; ys NULL = no image output.
+template <typename T, int FMT>
+auto codes_fill(const void* const* codes, void* const* ys, const int* hs, const int* ws, void* const* taps) {
+  return [=](CodesTable<T>& tab, int j, int i) {
+    tab.codes[j] = codes[i];
+    tab.y[j] = ys ? static_cast<T*>(ys[i]) : nullptr;
+    tab.taps[j] = FMT == kTapNone ? nullptr : static_cast<char*>(taps[i]);
+    tab.hw[j] = hs[i] * ws[i];
+    return ragged_addr(codes[i]) | ragged_addr(tab.y[j]) | (tap_vector_store<T, FMT>() ? ragged_addr(tab.taps[j]) : 0);
+  };
 }
 
-// the checks of a codes pass that do not depend on its step loop, all before the first launch; EXPO_OK with *go = false:
-// nothing to do (n == 0)
-inline int codes_check_args(const int32_t* filter_ids, const float* params, int steps, const void* const* codes,
-                            int channels, int code_bits, const void* tables, int table_stride, void* const* ys,
-                            const int* hs, const int* ws, int n, int dtype, uint64_t tap_mask, int tap_format,
-                            void* const* taps, bool* go) {
-  *go = false;
-  if (n < 0) return fail(EXPO_E_BADARG, "n >= 0 required");
-  if (dtype != EXPO_F16 && dtype != EXPO_F32) return fail(EXPO_E_BADDTYPE, "dtype must be EXPO_F16 or EXPO_F32");
+// the scalar checks of a codes pass, in front of ragged_check_args
+inline int codes_check_scalars(int channels, int code_bits, int table_stride) {
   if (channels != 1 && channels != 3 && channels != 4) return fail(EXPO_E_BADARG, "channels must be 1, 3 or 4");
   if (code_bits != 8 && code_bits != 16) return fail(EXPO_E_BADARG, "code_bits must be 8 or 16");
   if (table_stride != 0 && table_stride < (1 << code_bits))
     return fail(EXPO_E_BADARG, "table_stride must be 0 (one shared table) or at least 2^code_bits entries");
-  if (steps < 0 || steps > 64) return fail(EXPO_E_BADARG, "steps must be in [0, 64]");
-  if (int rc = check_taps(steps, tap_mask, tap_format)) return rc;
-  if (!ys && !tap_mask) return fail(EXPO_E_BADARG, "nothing to write (ys NULL and tap_mask 0)");
-  if (n == 0) return EXPO_OK;
-  if (!codes || !tables || !hs || !ws || (tap_mask && !taps) || (steps > 0 && (!filter_ids || !params)))
-    return fail(EXPO_E_BADARG, "null pointer");
-  if ((reinterpret_cast<uintptr_t>(tables) & 3) != 0) return fail(EXPO_E_BADARG, "tables must be 4-byte aligned");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_common(1, hs[i], ws[i], dtype)) return rc;
-    if (long(hs[i]) * ws[i] * channels * (code_bits / 8) > (1L << 31) - 8192)
-      return fail(EXPO_E_BADARG, "the codes of one image must be smaller than 2 GiB");
-    if (!codes[i] || (ys && !ys[i])) return fail(EXPO_E_BADARG, "null image pointer");
-    if (tap_mask && !taps[i]) return fail(EXPO_E_BADARG, "null tap pointer");
-  }
-  *go = true;
   return EXPO_OK;
+}
+
+// the pointer-stage checks of a codes pass, ragged_check_args' `extra`: the tables' alignment (i < 0), the bytes of
+// image i's codes
+inline auto codes_check_extra(const void* tables, const int* hs, const int* ws, int channels, int code_bits) {
+  return [=](int i) {
+    if (i < 0)
+      return (ragged_addr(tables) & 3) != 0 ? fail(EXPO_E_BADARG, "tables must be 4-byte aligned") : int(EXPO_OK);
+    return long(hs[i]) * ws[i] * channels * (code_bits / 8) > (1L << 31) - 8192
+               ? fail(EXPO_E_BADARG, "the codes of one image must be smaller than 2 GiB")
+               : int(EXPO_OK);
+  };
 }
 
 }  // namespace
