@@ -18,8 +18,9 @@ import subprocess
 
 import pytest
 
+from tests._policy_matrix_cases import TAP_NONE, TAP_STORAGE, TAP_U8, TAP_U16, ragged_plan
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TAP_STORAGE, TAP_U8, TAP_U16, TAP_NONE = 0, 1, 3, -1
 X, Y, TAPS = 0x10000, 0x20000, 0x30000  # aligned bases; an image's addresses are spaced out from them
 
 
@@ -53,29 +54,18 @@ def rehearse(tmp_path_factory):
 
 
 def expected(table, dtype, fmt, images, ys=True, stream_min_bytes=8 << 20):
-  ppl, ppv, size = (8, 2, 2) if dtype == 'f16' else (4, 1, 4)
-  tap_is_vector_stored = fmt == TAP_STORAGE or (fmt == TAP_U16 and dtype == 'f16')
-  stream = sum(h * w * 3 * size for h, w, _, _, _ in images) >= stream_min_bytes
+  """the rehearsal's text for the launches of the restated rule (tests/_policy_matrix_cases.py::ragged_plan, which
+  tests/test_hip_policy_matrix.py's ledger is computed from)"""
   out = []
-  for base in range(0, len(images), 64):
-    part = images[base:base + 64]
-    first, vec, slots = [0], 0, []
-    for j, (h, w, x, y, taps) in enumerate(part):
-      hw = h * w
-      y = y if ys else 0
-      taps = 0 if fmt == TAP_NONE else taps  # no tap kernel reads a tap pointer
-      groups = -(-hw // ppl)
-      first.append(first[-1] + -(-groups // 256))
-      aligned = x % 4 == 0 and y % 4 == 0 and (not tap_is_vector_stored or taps % 4 == 0)
-      if hw % ppv == 0 and aligned:
-        vec |= 1 << j
-      size_text = 'h=%d w=%d' % (h, w) if table == 'masked' else 'hw=%d' % hw
-      slots.append('  slot %d %s=0x%x y=0x%x %s%s' % (j, 'codes' if table == 'codes' else 'x', x, y, size_text,
-                                                     '' if table == 'ragged' else ' taps=0x%x' % taps))
-    any_slow = vec != (1 << len(part)) - 1
+  for launch in ragged_plan(dtype, fmt, images, ys, stream_min_bytes):
+    first = launch['first']
     out.append('launch stream=%d any_slow=%d grid=%d,1,1 base=%d n=%d first=%s vec=0x%x' %
-               (stream, any_slow, first[-1], base, len(part), ','.join(map(str, first)), vec))
-    out += slots
+               (launch['stream'], launch['any_slow'], first[-1], launch['base'], launch['n'],
+                ','.join(map(str, first)), launch['vec']))
+    for j, x, y, h, w, taps in launch['slots']:
+      size_text = 'h=%d w=%d' % (h, w) if table == 'masked' else 'hw=%d' % (h * w)
+      out.append('  slot %d %s=0x%x y=0x%x %s%s' % (j, 'codes' if table == 'codes' else 'x', x, y, size_text,
+                                                   '' if table == 'ragged' else ' taps=0x%x' % taps))
   return '\n'.join(out) + '\n'
 
 
