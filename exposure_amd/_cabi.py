@@ -52,6 +52,7 @@ SIGNATURES = {
     'expo_chain_plan': (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     'expo_chain_helper_stats': (_i, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'expo_chain_prepare': (_i, [_vp]),
+    'expo_chain_bwd_seq_launches': (ctypes.c_longlong, []),
     'expo_conv4x4s2_fwd': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     'expo_conv4x4s2_bwd_data': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
     'expo_conv_tuning': (_i, [_i, _i, _i]),
@@ -1756,6 +1757,13 @@ def chain_plan(n, h, w, dtype_code):
   buf = (ctypes.c_int * max(3 * count, 1))()
   _check(min(lib.expo_chain_plan(*args, buf, count, ctypes.byref(lanes), ctypes.byref(snake)), 0), 'expo_chain_plan')
   return [tuple(buf[3 * c:3 * c + 3]) for c in range(count)], lanes.value, bool(snake.value)
+
+
+def chain_bwd_seq_launches():
+  """How many run launches of expo_chain_bwd this process sent to a kernel compiled for the run's exact filter
+  sequence (expo_chain_bwd_seq_launches; one per run and lane).  Diagnostics: the results and the launch counts are
+  those of the general run kernels, so nothing else tells the two apart."""
+  return int(load().expo_chain_bwd_seq_launches())
 
 
 def chain_helper_stats():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
 # Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
-# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first;
+# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second;
 # extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
@@ -11,6 +11,9 @@
 #   chain_steps_bwd_rc.hip  the same runs with their interior activations recomputed from the run's lowest one
 #                        instead of loaded (the flags of exposure_hip.hip: its forward sweep must reproduce the
 #                        per-step forward kernels bit for bit, its backward steps the per-step backward kernels)
+#   chain_steps_bwd_seq.hip  the runs whose filter sequence is known at build time (the reference's filter order) as
+#                        straight-line kernels, one per sequence (the flags of exposure_hip.hip: every step must
+#                        reproduce the per-step kernels bit for bit)
 #   chain_fused.hip      the VALU-bound fused inference kernel (-fno-slp-vectorize -fno-honor-nans, see the file)
 #   chain_fused_codes.hip  the fused inference pass reading the files' integer codes (exactly chain_fused.hip's flags:
 #                        it includes that file for the step loop and the stores and must reproduce its outputs bit for bit)
@@ -91,6 +94,8 @@ p19=$!
 p20=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps_bwd_rc.hip" -o "$TMP/chain_steps_bwd_rc.o" &
 p21=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps_bwd_seq.hip" -o "$TMP/chain_steps_bwd_seq.o" &
+p22=$!
 wait $p1
 wait $p2
 wait $p3
@@ -112,5 +117,6 @@ wait $p18
 wait $p19
 wait $p20
 wait $p21
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" -o "$OUT"
+wait $p22
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

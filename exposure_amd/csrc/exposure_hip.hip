@@ -26,6 +26,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <mutex>
 #include <vector>
 #include <string>
@@ -1937,6 +1938,19 @@ static bool chain_bwd_recompute() {
   return on;
 }
 
+// May a run whose sequence chain_steps_bwd_seq.hip was compiled for go to that kernel?  EXPO_CHAIN_BWD_SEQ=0, read once
+// per process, keeps chain_steps_bwd_rc for every run: the A/B switch inside one build.
+static bool chain_bwd_seq() {
+  // (env_int takes only positive values: "0" is the setting that matters here)
+  static const bool on = [] {
+    const char* v = getenv("EXPO_CHAIN_BWD_SEQ");
+    return !v || !*v || atoi(v) != 0;
+  }();
+  return on;
+}
+// run launches that went to a compiled sequence (expo_chain_bwd_seq_launches)
+static std::atomic<long long> g_chain_bwd_seq_launches{0};
+
 extern "C" {
 
 int expo_version(void) { return EXPO_ABI_VERSION; }
@@ -2305,6 +2319,7 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts, void* co
     return cnt > 1 ? cnt : 1;
   };
   const bool recompute = chain_bwd_recompute();  // (a run's launch, not how runs are collected)
+  const bool seq_ok = recompute && chain_bwd_seq();
   for (size_t c = 0; c < plan.chunks.size() && !rc; ++c) {
     const ChainChunk& ck = plan.chunks[c];
     hipStream_t sp = ck.lane ? fj->helper : s;
@@ -2313,9 +2328,13 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts, void* co
     for (int i = steps - 1; i >= 0 && !rc; i -= cnt) {
       cnt = fuse > 1 ? run_from(i) : 1;
       if (cnt > 1) {
-        rc = (recompute ? chain_steps_bwd_rc : chain_steps_bwd)(filter_ids, i, cnt, acts, grads, params, records,
-                                                                 step_floats, ck.nb, ck.np, h, w, dtype, hsv_grad_mode,
-                                                                 n, sp);
+        // a sequence known at build time has a kernel of its own (chain_steps_bwd_seq.hip); it recomputes like
+        // chain_steps_bwd_rc, so only where that one would run
+        const bool seq = seq_ok && chain_steps_bwd_seq_has(filter_ids, i, cnt, dtype, hsv_grad_mode);
+        rc = (seq ? chain_steps_bwd_seq : recompute ? chain_steps_bwd_rc : chain_steps_bwd)(
+            filter_ids, i, cnt, acts, grads, params, records, step_floats, ck.nb, ck.np, h, w, dtype, hsv_grad_mode, n,
+            sp);
+        if (seq && !rc) g_chain_bwd_seq_launches.fetch_add(1, std::memory_order_relaxed);
         continue;
       }
       // the forward launch of step steps-1 walked in direction (steps-1) & 1 and ENDED on the other side: the backward
@@ -2342,6 +2361,8 @@ int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts, void* co
   if (rc) return rc;
   return expo_finish_bwd(filter_ids, steps, params, dparams, n, h, w, dtype, workspace, workspace_bytes, stream);
 }
+
+long long expo_chain_bwd_seq_launches(void) { return g_chain_bwd_seq_launches.load(std::memory_order_relaxed); }
 
 int expo_critic_stats(const void* x, float* stats, int n, int h, int w, int dtype, void* workspace,
                       size_t workspace_bytes, void* stream) {

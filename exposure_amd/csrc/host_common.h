@@ -139,6 +139,13 @@ bool chain_steps_bwd_recomputes(int id, int dtype);
 int chain_steps_bwd_rc(const int* ids, int i0, int cnt, void* const* acts, void* const* grads,
                        const float* const* params, float* records, size_t step_floats, int nb, int np, int h, int w,
                        int dtype, int mode, int n_geom, hipStream_t s);
+// defined in chain_steps_bwd_seq.hip, used by expo_chain_bwd: chain_steps_bwd_rc for the runs whose ids (from the head
+// i0 down), storage type and mode are in that unit's static table EXPO_RUN_SEQUENCES (chain_steps_bwd_seq_has) -- the
+// same arguments, launch geometry and results from a kernel compiled for exactly that sequence.
+bool chain_steps_bwd_seq_has(const int* ids, int i0, int cnt, int dtype, int mode);
+int chain_steps_bwd_seq(const int* ids, int i0, int cnt, void* const* acts, void* const* grads,
+                        const float* const* params, float* records, size_t step_floats, int nb, int np, int h, int w,
+                        int dtype, int mode, int n_geom, hipStream_t s);
 
 inline int check_common(int n, int h, int w, int dtype) {
   if (n < 0 || h < 1 || w < 1) return fail(EXPO_E_BADARG, "n >= 0, h >= 1, w >= 1 required");

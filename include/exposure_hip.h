@@ -301,11 +301,19 @@ int expo_chain_fwd(const int* filter_ids, int steps, void* const* acts,
  *            acts[i] of such a run are NOT read.  A caller that edits activations between the forward
  *            and the backward sets EXPO_CHAIN_BWD_RECOMPUTE=0 in the environment (read once per
  *            process): every step then reads its acts[i], with the same results for unedited ones.
+ *
+ * A run whose filter ids, storage type and hsv_grad_mode are in the library's table of compiled sequences (the
+ * reference's filter order: Saturation+, White balance, Gamma, Exposure from the run's head down)
+ * goes to a kernel compiled for exactly that sequence, with the same launch count and bit-identical results.
+ * EXPO_CHAIN_BWD_SEQ=0 in the environment (read once per process) keeps the general kernels for every run.
+ * expo_chain_bwd_seq_launches() returns how many run launches of this process went to a compiled sequence (one per
+ * run and lane; diagnostics -- nothing else tells the two kernels apart).
  */
 int expo_chain_bwd(const int* filter_ids, int steps, void* const* acts,
                    void* const* grads, const float* const* params,
                    float* const* dparams, int n, int h, int w, int dtype,
                    int hsv_grad_mode, void* workspace, size_t workspace_bytes, void* stream);
+long long expo_chain_bwd_seq_launches(void);
 
 /*
  * Fused multi-step forward for the high-resolution inference path (net.py:796-821, evaluate.py:8-31):
