@@ -120,6 +120,11 @@ SIGNATURES = {
     'expo_png_encode_workspace_bytes': (_sz, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
     'expo_png_encode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, ctypes.POINTER(_vp),
                                     ctypes.POINTER(ctypes.c_int64), _vp, _vp, _sz, _vp]),
+    'expo_jpeg_restart_mcus': (_i, [_i]),
+    'expo_jpeg_encode_bound': (ctypes.c_int64, [_i, _i, _i]),
+    'expo_jpeg_encode_workspace_bytes': (_sz, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
+    'expo_jpeg_encode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i,
+                                     ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), _vp, _vp, _sz, _vp]),
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -1107,6 +1112,97 @@ def png_encode_ragged(pictures, filter='adaptive', outs=None, workspace=None):
     _check(lib.expo_png_encode_ragged(_ptr_array(pictures), hsa, wsa, n, filter, _ptr_array(outs), caps, _ptr(sizes),
                                       _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
            'expo_png_encode_ragged')
+  return outs, sizes
+
+
+JPEG_SUBSAMPLING = ('444', '420')  # expo_jpeg_encode_ragged's subsampling 0 and 2 (PIL's numbers)
+JPEG_HEADER_BYTES = 629
+_JPEG_SUBSAMPLING_CODE = {'444': 0, '420': 2, 0: 0, 2: 2}
+
+
+def _jpeg_subsampling(subsampling):
+  if subsampling not in _JPEG_SUBSAMPLING_CODE:
+    raise ExposureHipError("exposure_amd: subsampling must be '444' or '420' (or 0 / 2), got %r" % (subsampling,))
+  return _JPEG_SUBSAMPLING_CODE[subsampling]
+
+
+def jpeg_restart_mcus(subsampling='420'):
+  """``expo_jpeg_restart_mcus``: the MCUs of one restart interval of a sampling."""
+  return int(load().expo_jpeg_restart_mcus(_jpeg_subsampling(subsampling)))
+
+
+def jpeg_encode_bound(h, w, subsampling='420'):
+  """``expo_jpeg_encode_bound``: a proved upper bound of the file of an (h, w, 3) picture (several times raw)."""
+  bound = int(load().expo_jpeg_encode_bound(int(h), int(w), _jpeg_subsampling(subsampling)))
+  if bound < 0:
+    _check(-1, 'expo_jpeg_encode_bound')  # EXPO_E_BADARG, with the library's message
+  return bound
+
+
+def jpeg_encode_workspace_bytes(hs, ws, subsampling='420'):
+  """``expo_jpeg_encode_workspace_bytes``: the scratch of a call on pictures of these sizes (0 for invalid ones)."""
+  n = len(hs)
+  return int(load().expo_jpeg_encode_workspace_bytes((ctypes.c_int * n)(*[int(h) for h in hs]),
+                                                     (ctypes.c_int * n)(*[int(w) for w in ws]), n,
+                                                     _jpeg_subsampling(subsampling)))
+
+
+def jpeg_encode_ragged(pictures, quality=90, subsampling='420', capacity=None, outs=None, workspace=None):
+  """``expo_jpeg_encode_ragged``: baseline JPEG files of N pictures, made on the device -> (outs, sizes).  pictures: N
+  contiguous (H_i, W_i, 3) uint8 RGB tensors on one ROCm device; quality 1..100; subsampling '444' or '420'; capacity:
+  the bytes of every output buffer (an int, or one per picture; default 629 + H_i W_i 3, ``jpeg_encode_bound`` makes an
+  overflow impossible); outs: N contiguous uint8 device tensors to write into instead (their sizes are the capacities).
+  sizes is an int64 device tensor (N,) of the files' true lengths; file i is ``outs[i][:sizes[i]]`` iff
+  ``sizes[i] <= outs[i].numel()``, otherwise ``outs[i]`` is untouched.  Nothing is downloaded and the host is not waited
+  for.  The shared workspace serves the call unless ``workspace=`` is given."""
+  lib = load()
+  n = len(pictures)
+  sub = _jpeg_subsampling(subsampling)
+  quality = int(quality)
+  if not 1 <= quality <= 100:
+    raise ExposureHipError('exposure_amd: quality must be in 1..100, got %d' % quality)
+  if outs is not None and len(outs) != n:
+    raise ExposureHipError('exposure_amd: pictures and outs must have the same length')
+  if n == 0:
+    return [], None
+  if not isinstance(pictures[0], torch.Tensor) or not pictures[0].is_cuda:
+    raise ExposureHipError('exposure_amd: pictures must be tensors on a ROCm device (HIP path only, no CPU fallback)')
+  device = pictures[0].device
+  for i, p in enumerate(pictures):
+    if not isinstance(p, torch.Tensor) or p.dtype is not torch.uint8 or p.dim() != 3 or p.shape[2] != 3 or \
+        p.device != device or not p.is_contiguous() or p.numel() == 0:
+      raise ExposureHipError('exposure_amd: pictures[%d] must be a contiguous (H, W, 3) uint8 tensor on %s' % (i, device))
+  hs, ws = [int(p.shape[0]) for p in pictures], [int(p.shape[1]) for p in pictures]
+  for h, w in zip(hs, ws):
+    jpeg_encode_bound(h, w, sub)  # raises for a side beyond 65535
+  if outs is None:
+    if capacity is None:
+      capacity = [JPEG_HEADER_BYTES + h * w * 3 for h, w in zip(hs, ws)]
+    elif isinstance(capacity, int):
+      capacity = [capacity] * n
+    if len(capacity) != n or any(int(c) < 0 for c in capacity):
+      raise ExposureHipError('exposure_amd: capacity must be a non-negative int or one per picture')
+    outs = [torch.empty((max(int(c), 1),), dtype=torch.uint8, device=device) for c in capacity]
+    caps = [int(c) for c in capacity]
+  else:
+    for i, o in enumerate(outs):
+      if not isinstance(o, torch.Tensor) or o.dtype is not torch.uint8 or o.device != device or not o.is_contiguous() or \
+          o.numel() == 0:
+        raise ExposureHipError('exposure_amd: outs[%d] must be a contiguous, non-empty uint8 tensor on %s' % (i, device))
+    caps = [o.numel() for o in outs]
+  sizes = torch.empty((n,), dtype=torch.int64, device=device)
+  hsa, wsa = (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws)
+  with torch.cuda.device(device):
+    need = int(lib.expo_jpeg_encode_workspace_bytes(hsa, wsa, n, sub))
+    if workspace is None:
+      workspace = reserve_workspace(device, need)
+      _order_shared_workspace(device)
+    if not workspace.is_cuda or workspace.device != device or workspace.numel() * workspace.element_size() < need:
+      raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' % (need, device))
+    _check(lib.expo_jpeg_encode_ragged(_ptr_array(pictures), hsa, wsa, n, quality, sub, _ptr_array(outs),
+                                       (ctypes.c_int64 * n)(*caps), _ptr(sizes), _ptr(workspace),
+                                       workspace.numel() * workspace.element_size(), _stream()),
+           'expo_jpeg_encode_ragged')
   return outs, sizes
 
 

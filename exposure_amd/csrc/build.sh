@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
 # Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
-# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second;
+# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second, and jpeg_encode.hip, the twenty-third;
 # extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
@@ -42,6 +42,9 @@
 #   png_encode.hip      8-bit PNG files made on the device: the row filter and a Huffman-only deflate in independent
 #                        segments (default flags: integer code; png_deflate.h holds its serial routines, which
 #                        tools/png_rehearse.cpp runs on the host)
+#   jpeg_encode.hip     baseline JPEG files made on the device: colour conversion, 8 x 8 transform, quantisation and the
+#                        fixed Huffman code in independent restart intervals (default flags: integer code; jpeg_codec.h
+#                        holds its serial routines, which tools/jpeg_rehearse.cpp runs on the host)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -96,6 +99,8 @@ p20=$!
 p21=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/chain_steps_bwd_seq.hip" -o "$TMP/chain_steps_bwd_seq.o" &
 p22=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/jpeg_encode.hip" -o "$TMP/jpeg_encode.o" &
+p23=$!
 wait $p1
 wait $p2
 wait $p3
@@ -118,5 +123,6 @@ wait $p19
 wait $p20
 wait $p21
 wait $p22
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" -o "$OUT"
+wait $p23
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" "$TMP/jpeg_encode.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -11,7 +11,8 @@ Image decoding (16-bit TIFF / ProPhoto linearisation, ``util.py:311-323, 495-501
 outputs of ``net.py:825-877`` the CLI writes the linear result (.npy) and, with ``--png``, the reference's 8-bit
 ``retouched`` / ``input_tone_mapped`` pictures; with ``--step-by-step`` also the ``intermediateNN`` pictures of
 ``net.py:820-823`` (``evaluate.py:31``); the debug pickle and the cv2-drawn ``steps`` panel are out of scope.
-``--tiff16`` writes the pictures as 16-bit TIFFs instead, the depth the input files have.
+``--tiff16`` writes the pictures as 16-bit TIFFs instead, the depth the input files have; ``--device-jpeg-encode``
+writes them as baseline JPEG files encoded on the GPU (``encode_jpeg_batch``).
 """
 import warnings
 
@@ -804,6 +805,31 @@ def save_png_bytes(path, data):
   return path
 
 
+JPEG_SUBSAMPLING = ('444', '420')  # the samplings of encode_jpeg_batch (_cabi.JPEG_SUBSAMPLING)
+
+
+def encode_jpeg_batch(pictures, quality=90, subsampling='420'):
+  """The baseline JPEG files of (H_i, W_i, 3) uint8 device pictures (``encode_u8``, EXPO_TAP_U8 taps,
+  ``input_pictures_raw``) as ``bytes``, encoded on the device in one ragged call (``expo_jpeg_encode_ragged``, DESIGN.md
+  3.34) into buffers of 629 + H W 3 bytes.  The download of the files' lengths is the only synchronise; then the used
+  prefix of every buffer is copied out.  A file longer than its buffer (noise at quality 100) is not written by that
+  call: those pictures are encoded once more, in one call, into buffers of the reported lengths."""
+  from . import _cabi
+  pictures = [p.contiguous() for p in pictures]
+  if not pictures:
+    return []
+  outs, sizes = _cabi.jpeg_encode_ragged(pictures, quality, subsampling)
+  sizes = sizes.cpu().tolist()
+  files = [o[:n].cpu().numpy().tobytes() if n <= o.numel() else None for o, n in zip(outs, sizes)]
+  again = [i for i, f in enumerate(files) if f is None]
+  if again:
+    outs, _ = _cabi.jpeg_encode_ragged([pictures[i] for i in again], quality, subsampling,
+                                       capacity=[sizes[i] for i in again])
+    for i, o in zip(again, outs):
+      files[i] = o[:sizes[i]].cpu().numpy().tobytes()
+  return files
+
+
 def save_tiff_u16(path, img_u16):
   """An (H, W, 3) uint16 array (``encode_u16``, or an EXPO_TAP_U16 tap) as an uncompressed 16-bit RGB TIFF: the file's
   payload is the array byte for byte."""
@@ -953,6 +979,16 @@ def main(argv=None):
   ap.add_argument('--png-filter', default='adaptive', choices=list(PNG_FILTERS),
                   help='the row filter of --device-png-encode: one type for every row, or adaptive (per row the type '
                   'with the smallest sum of absolute residuals, libpng\'s heuristic)')
+  ap.add_argument('--device-jpeg-encode', action='store_true',
+                  help='write a baseline JPEG, encoded on the GPU (encode_jpeg_batch: transform, quantisation and the '
+                  'standard Huffman code in independent restart intervals, DESIGN.md 3.34), for every picture for which '
+                  '--device-png-encode writes a PNG, under the same name with .jpg: <output>.jpg, the --step-by-step '
+                  'intermediates and the --device-input-png pictures, one call per group of --batch images and kind; the '
+                  'records list them under jpeg.  Implies --device-png; not with --device-png-encode or --tiff16')
+  ap.add_argument('--jpeg-quality', type=int, default=90, metavar='Q',
+                  help='the quality of --device-jpeg-encode, 1..100 (libjpeg\'s scaling of the Annex K tables)')
+  ap.add_argument('--jpeg-subsampling', default='420', choices=list(JPEG_SUBSAMPLING),
+                  help='the chroma sampling of --device-jpeg-encode: 444 or 420')
   ap.add_argument('--tiff16', action='store_true',
                   help='write the pictures as 16-bit RGB TIFFs (uncompressed, little-endian) instead of 8-bit PNGs: '
                   '<output>.tif and, with --step-by-step, <output>.intermediateNN.tif, code = round(value * 65535) '
@@ -1000,10 +1036,14 @@ def main(argv=None):
   dt = torch.float16 if args.dtype == 'f16' else torch.float32
   if args.batch < 1:
     ap.error('--batch must be >= 1')
+  if args.device_jpeg_encode and (args.device_png_encode or args.tiff16):
+    ap.error('--device-jpeg-encode does not go with --device-png-encode or --tiff16: a picture is written once')
+  if not 1 <= args.jpeg_quality <= 100:
+    ap.error('--jpeg-quality must be in 1..100')
   if args.tiff16 and (args.png or args.device_png or args.score or args.device_png_encode):
     ap.error('--tiff16 does not go with --png, --device-png, --device-png-encode or --score: they need the 8-bit '
              'pictures, and one pass makes pictures of one depth')
-  if args.device_png_encode:
+  if args.device_png_encode or args.device_jpeg_encode:
     args.device_png = True
   if args.score:
     args.device_png = True
@@ -1041,25 +1081,30 @@ def main(argv=None):
     return [dict(zip(show, per)) for per in zip(*made)]
 
   def encode_group(pics, inters, inps):
-    """--device-png-encode: per image of a group its finished PNG files by name, one device call per kind (the
-    retouched pictures, the intermediates, the input pictures)"""
+    """--device-png-encode, --device-jpeg-encode: per image of a group its finished PNG (JPEG) files by name, one
+    device call per kind (the retouched pictures, the intermediates, the input pictures)"""
+    if args.device_jpeg_encode:
+      encode = lambda pictures: encode_jpeg_batch(pictures, args.jpeg_quality, args.jpeg_subsampling)
+    else:
+      encode = lambda pictures: encode_png_batch(pictures, args.png_filter)
     files = [dict() for _ in pics]
-    for i, data in enumerate(encode_png_batch(pics, args.png_filter)):
+    for i, data in enumerate(encode(pics)):
       files[i]['retouched'] = data
     if inters is not None:
       keys = [(i, s) for i, inter in enumerate(inters) for s in range(inter.shape[0])]
-      for (i, s), data in zip(keys, encode_png_batch([inters[i][s] for i, s in keys], args.png_filter)):
+      for (i, s), data in zip(keys, encode([inters[i][s] for i, s in keys])):
         files[i]['intermediate%02d' % s] = data
     if inps:
       keys = [(i, name) for i in range(len(pics)) for name in show]
-      for (i, name), data in zip(keys, encode_png_batch([inps[i][name] for i, name in keys], args.png_filter)):
+      for (i, name), data in zip(keys, encode([inps[i][name] for i, name in keys])):
         files[i][name] = data
     return files
 
   def save_picture(path, key, files, tensor):
-    """an 8-bit device picture as a PNG: the file the device encoded, or PIL's of the downloaded values"""
+    """an 8-bit device picture as a PNG: the file the device encoded (with --device-jpeg-encode a JPEG, under the
+    same name with .jpg), or PIL's of the downloaded values"""
     if files is not None and key in files:
-      return save_png_bytes(path, files[key])
+      return save_png_bytes(path[:-4] + '.jpg' if args.device_jpeg_encode else path, files[key])
     return save_png_u8(path, tensor.cpu().numpy())
 
   def save_input_pngs(pngs, stem, hi, inp, files=None):
@@ -1101,13 +1146,16 @@ def main(argv=None):
       save_input_pngs(pngs, stem, hi, inp, files)
       if inter is not None and files is not None:
         for i in range(inter.shape[0]):
-          pngs['intermediate%02d' % i] = save_png_bytes('%s.intermediate%02d.png' % (stem, i), files['intermediate%02d' % i])
+          pngs['intermediate%02d' % i] = save_picture('%s.intermediate%02d.png' % (stem, i), 'intermediate%02d' % i, files, None)
       elif inter is not None:
         for i, a in enumerate(inter.cpu().numpy()):
           pngs['intermediate%02d' % i] = save_png_u8('%s.intermediate%02d.png' % (stem, i), a)
     records.append(dict(image=path, output=None if args.pictures_only else dst, png=pngs, tiff=tiffs, filters=names, states=states[0].cpu().tolist(),
                         abi_filter_ids=ops['abi_filter_ids'][0].cpu().tolist(),
                         params24=ops['params24'][0].cpu().numpy()))
+    if args.device_jpeg_encode:  # the files the device encoded are JPEGs: listed under their own key
+      records[-1]['jpeg'] = {k: v for k, v in pngs.items() if files is not None and k in files}
+      records[-1]['png'] = {k: v for k, v in pngs.items() if k not in records[-1]['jpeg']}
 
   def load(path):
     return torch.from_numpy(np.ascontiguousarray(load_image(path))).to(dev).to(dt)[None]
@@ -1124,11 +1172,12 @@ def main(argv=None):
 
   def emit_batch(paths, his, res, inps=None):
     outs, states, ops = res[0], res[2], res[3]
-    files = encode_group(list(res[-1]), list(res[4]) if inter_kind else None, inps) if args.device_png_encode else None
+    files = encode_group(list(res[-1]), list(res[4]) if inter_kind else None, inps) if encode_files else None
     for i, (path, hi, out) in enumerate(zip(paths, his, outs)):
       emit(path, hi, out, states[i:i + 1], {k: v[i:i + 1] for k, v in ops.items()}, res[4][i] if inter_kind else None,
            res[-1][i] if picture else None, inps[i] if inps else None, files[i] if files else None)
 
+  encode_files = args.device_png_encode or args.device_jpeg_encode
   if args.fused_decode:  # also with --batch 1: groups of one image
     for b in range(0, len(args.images), args.batch):
       paths = args.images[b:b + args.batch]
@@ -1144,7 +1193,7 @@ def main(argv=None):
       res = retouch(agent, hi, return_trace='full', fused=not args.stepwise, intermediates=inter_kind, proxy=proxy,
                     picture=picture, masks=masks, curves=curves)
       inter = res[4][:, 0] if inter_kind else None
-      files = encode_group([res[-1][0]], [inter] if inter_kind else None, inps) if args.device_png_encode else None
+      files = encode_group([res[-1][0]], [inter] if inter_kind else None, inps) if encode_files else None
       emit(path, hi, res[0], res[2], res[3], inter, res[-1][0] if picture else None, inps[0] if inps else None,
            files[0] if files else None)
   else:

@@ -61,7 +61,9 @@ extern "C" {
                               expo_chain_fused_fwd_ragged_codes, expo_codes_max_ragged,
                               expo_codes_lut_ragged, expo_chain_fused_curves_fwd_ragged,
                               expo_chain_fused_curves_fwd_ragged_codes, expo_png_segment_bytes,
-                              expo_png_encode_bound, expo_png_encode_workspace_bytes, expo_png_encode_ragged */
+                              expo_png_encode_bound, expo_png_encode_workspace_bytes, expo_png_encode_ragged,
+                              expo_jpeg_restart_mcus, expo_jpeg_encode_bound, expo_jpeg_encode_workspace_bytes,
+                              expo_jpeg_encode_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -583,6 +585,48 @@ size_t expo_png_encode_workspace_bytes(const int* hs, const int* ws, int n);
 int expo_png_encode_ragged(const void* const* pics, const int* hs, const int* ws, int n, int filter, void* const* outs,
                            const int64_t* out_capacity, int64_t* sizes, void* workspace, size_t workspace_bytes,
                            void* stream);
+
+/*
+ * Baseline JPEG files made on the device (jpeg_encode.hip): the photographer's deliverable of the
+ * pictures show_and_save writes (net.py:769-772), without a host encoder.  Added exports of ABI 9 (the version is
+ * unchanged).
+ *
+ * The file (DESIGN.md §3.34 fixes every byte): SOI; APP0 JFIF 1.01, density 1 x 1; DQT 0 and 1 (T.81 Annex K.1 / K.2
+ * scaled by `quality` as libjpeg does, 8-bit, zigzag order); SOF0 (precision 8, three components, Y sampled 1 x 1 for
+ * subsampling 0 and 2 x 2 for subsampling 2); the four DHT of Annex K.3 - K.6; DRI; SOS; the restart intervals; EOI.
+ * The header is 629 bytes.  Colour: the JFIF integer matrix in 16-bit fixed point; planes extended to whole MCUs by
+ * edge replication; 4:2:0 chroma is the rounded mean of 2 x 2.  Transform: two 8-point passes with the 13-bit cosine
+ * table of csrc/jpeg_codec.h, everything in int32.  An interval is Ri MCUs in raster order, coded on its own with the
+ * DC predictors at 0, padded to a byte with 1-bits, 0xFF stuffed, followed by RSTm (m = k mod 8) unless it is the last.
+ * The bytes depend on the picture, `quality` and `subsampling` alone.
+ *
+ * expo_jpeg_restart_mcus (net.py:769-772): Ri of a sampling, a compile-time constant (16 and 8: 48 blocks either way); -1 (with a message)
+ *   for a subsampling other than 0 (4:4:4) and 2 (4:2:0).
+ * expo_jpeg_encode_bound (net.py:769-772): a proved upper bound of the file's length: 629 + per interval of m MCUs of
+ *   B blocks (3 or 6) 2 ceil(1660 m B / 8) + 2 -- a block is at most 22 + 63 * 26 = 1660 bits, stuffing at most doubles
+ *   the padded bytes, and two bytes of marker follow.  -1 (with a message) when h or w is outside 1..65535.
+ * expo_jpeg_encode_workspace_bytes (net.py:769-772): the scratch a call on these n pictures needs (0 for invalid
+ *   arguments): per picture of a launch group 16 bytes, and 4 + 8 bytes per interval, each piece rounded up to 16.
+ * expo_jpeg_encode_ragged (net.py:769-772):
+ *   pics         HOST array of n device pointers, picture i is contiguous [hs[i]][ws[i]][3] uint8 RGB, any alignment.
+ *   quality      1..100; subsampling 0 (4:4:4) or 2 (4:2:0).
+ *   outs         HOST array of n device pointers to byte buffers, any alignment; out_capacity HOST [n], each >= 0.
+ *                File i is written iff sizes[i] <= out_capacity[i], as outs[i][0 .. sizes[i]); otherwise not one byte
+ *                of outs[i] is written.  A capacity of expo_jpeg_encode_bound makes that impossible.
+ *   sizes        DEVICE int64 [n]: the files' true lengths, whatever the capacities.
+ *   workspace    caller-owned, 16-byte aligned device scratch of at least expo_jpeg_encode_workspace_bytes(...) bytes;
+ *                needs no initialisation and carries no state.
+ * Allocates nothing, does not synchronise with the host, can be captured.  64 pictures per launch group (three
+ * launches), more as further groups on `stream`.  Everything is validated before anything is enqueued (EXPO_E_BADARG:
+ * n < 0, quality outside 1..100, a subsampling other than 0 and 2, h or w outside 1..65535, a negative capacity, a
+ * workspace that is too small or misaligned, null pointers); n == 0 is a no-op.
+ */
+int expo_jpeg_restart_mcus(int subsampling);
+int64_t expo_jpeg_encode_bound(int h, int w, int subsampling);
+size_t expo_jpeg_encode_workspace_bytes(const int* hs, const int* ws, int n, int subsampling);
+int expo_jpeg_encode_ragged(const void* const* pics, const int* hs, const int* ws, int n, int quality, int subsampling,
+                            void* const* outs, const int64_t* out_capacity, int64_t* sizes, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /*
  * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of
