@@ -7,10 +7,18 @@
 * ``cnn`` / ``critic`` (+ value network)     ``critics.py:6-98``
 * the loss graph of the trainer              ``net.py:92-194``
 
-TEST INFRASTRUCTURE ONLY (see ``oracle/__init__.py``); PARITY UNPINNED by the reference (no tests, no
-fixtures, TensorFlow absent).  Pinned instead by: float64 finite differences of the hand-written
-backward passes (``tests/test_oracle_nets.py``), TF's documented SAME-padding arithmetic restated
-below, and agreement with the torch modules of ``exposure_amd`` holding the SAME weights.
+TEST INFRASTRUCTURE ONLY (see ``oracle/__init__.py``).  COMPOSITION PINNED by the reference's own text:
+``tests/golden/make_reference_train_graph.py`` cuts ``cnn`` / ``critic``, ``feature_extractor``,
+``enrich_image_input``, ``agent_generator``, the filter classes and the loss statements of ``net.py`` out of
+the reference by ``ast`` and executes them under a torch float64 stand-in for ``tf``;
+``tests/test_reference_train_graph.py`` holds every value of this file to the recorded ones (1e-10) and
+central differences of its losses, stop-gradient operands frozen, to the recorded gradients (1e-6) -- which
+operand is stopped, what ``emd`` is taken from, which states feed the value net, the plane order, the NHWC
+flatten, the variable names.  STILL UNPINNED: the primitives (TensorFlow is absent; the stand-in's SAME
+padding, tie and clip conventions are the ones listed below, written by the same hand).  Also held by: float64
+finite differences of the hand-written backward passes (``tests/test_oracle_nets.py``), TF's documented
+SAME-padding arithmetic restated below, and agreement with the torch modules of ``exposure_amd`` holding the
+SAME weights.
 
 Weights are passed as ``{tf_variable_name: ndarray}`` in TF-1 layout -- ``ly.conv2d`` kernels HWIO,
 ``ly.fully_connected`` weights (in, out) -- with the variable scopes of the reference graph
