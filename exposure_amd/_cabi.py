@@ -125,6 +125,11 @@ SIGNATURES = {
     'expo_jpeg_encode_workspace_bytes': (_sz, [ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
     'expo_jpeg_encode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i, _i,
                                      ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), _vp, _vp, _sz, _vp]),
+    'expo_jpeg_decode_plan_bytes': (_sz, [_i]),
+    'expo_jpeg_decode_workspace_bytes': (_sz, [ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    'expo_jpeg_decode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_vp), ctypes.POINTER(_i),
+                                    ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i,
+                                    ctypes.POINTER(_vp), _vp, _vp, _sz, _vp]),
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -1204,6 +1209,63 @@ def jpeg_encode_ragged(pictures, quality=90, subsampling='420', capacity=None, o
                                        workspace.numel() * workspace.element_size(), _stream()),
            'expo_jpeg_encode_ragged')
   return outs, sizes
+
+
+def jpeg_decode_plan_bytes(nsegs):
+  """``expo_jpeg_decode_plan_bytes``: the bytes of the plan of a file of ``nsegs`` restart intervals."""
+  return int(load().expo_jpeg_decode_plan_bytes(int(nsegs)))
+
+
+def jpeg_decode_workspace_bytes(hs, ws, samplings, ncomps):
+  """``expo_jpeg_decode_workspace_bytes``: the scratch of a call on files of these geometries (0 for invalid ones)."""
+  n = len(hs)
+  arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+  return int(load().expo_jpeg_decode_workspace_bytes(arr(hs), arr(ws), arr(samplings), arr(ncomps), n))
+
+
+def jpeg_decode_ragged(files, plans, hs, ws, samplings, ncomps, nsegs, outs, status, workspace=None):
+  """``expo_jpeg_decode_ragged``: N baseline JPEG files decoded on the device.  files: N contiguous uint8 device tensors
+  (the files' bytes, any alignment); plans: N contiguous uint8 device tensors, 16-byte aligned (the blobs of
+  ``jpeg_decode.parse``); hs, ws, samplings (0 / 1 / 2), ncomps (1 / 3), nsegs: the host geometry; outs: N contiguous
+  (H_i, W_i, 3) uint8 device tensors (any alignment); status: a contiguous int32 device tensor (N,), written for every
+  picture.  Nothing is downloaded and the host is not waited for.  The shared workspace serves the call unless
+  ``workspace=`` is given."""
+  lib = load()
+  n = len(files)
+  if not (len(plans) == len(hs) == len(ws) == len(samplings) == len(ncomps) == len(nsegs) == len(outs) == n):
+    raise ExposureHipError('exposure_amd: files, plans, the geometry and outs must have the same length')
+  if n == 0:
+    return
+  if not isinstance(files[0], torch.Tensor) or not files[0].is_cuda:
+    raise ExposureHipError('exposure_amd: files must be tensors on a ROCm device (HIP path only, no CPU fallback)')
+  device = files[0].device
+  for what, seq in (('files', files), ('plans', plans), ('outs', outs)):
+    for i, t in enumerate(seq):
+      if not isinstance(t, torch.Tensor) or t.dtype is not torch.uint8 or t.device != device or not t.is_contiguous() or \
+          t.numel() == 0:
+        raise ExposureHipError('exposure_amd: %s[%d] must be a contiguous, non-empty uint8 tensor on %s' % (what, i, device))
+  for i, (o, h, w) in enumerate(zip(outs, hs, ws)):
+    if o.numel() != int(h) * int(w) * 3:
+      raise ExposureHipError('exposure_amd: outs[%d] must hold %d x %d x 3 bytes' % (i, h, w))
+  for i, (p, k) in enumerate(zip(plans, nsegs)):
+    if p.numel() < jpeg_decode_plan_bytes(k):
+      raise ExposureHipError('exposure_amd: plans[%d] is smaller than the plan of %d segments' % (i, k))
+  if not isinstance(status, torch.Tensor) or status.dtype is not torch.int32 or status.device != device or \
+      not status.is_contiguous() or status.numel() != n:
+    raise ExposureHipError('exposure_amd: status must be a contiguous int32 tensor (%d,) on %s' % (n, device))
+  arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+  hsa, wsa, sa, ca = arr(hs), arr(ws), arr(samplings), arr(ncomps)
+  with torch.cuda.device(device):
+    need = int(lib.expo_jpeg_decode_workspace_bytes(hsa, wsa, sa, ca, n))
+    if workspace is None:
+      workspace = reserve_workspace(device, need)
+      _order_shared_workspace(device)
+    if not workspace.is_cuda or workspace.device != device or workspace.numel() * workspace.element_size() < need:
+      raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' % (need, device))
+    _check(lib.expo_jpeg_decode_ragged(_ptr_array(files), (ctypes.c_int64 * n)(*[f.numel() for f in files]), _ptr_array(plans),
+                                       hsa, wsa, sa, ca, arr(nsegs), n, _ptr_array(outs), _ptr(status), _ptr(workspace),
+                                       workspace.numel() * workspace.element_size(), _stream()),
+           'expo_jpeg_decode_ragged')
 
 
 def area_resize_ragged(xs, windows, S, out):

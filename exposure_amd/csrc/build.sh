@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
 # Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
-# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second, and jpeg_encode.hip, the twenty-third;
+# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second, and jpeg_encode.hip, the twenty-third, and jpeg_decode.hip, the twenty-fourth;
 # extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
@@ -45,6 +45,9 @@
 #   jpeg_encode.hip     baseline JPEG files made on the device: colour conversion, 8 x 8 transform, quantisation and the
 #                        fixed Huffman code in independent restart intervals (default flags: integer code; jpeg_codec.h
 #                        holds its serial routines, which tools/jpeg_rehearse.cpp runs on the host)
+#   jpeg_decode.hip     baseline JPEG files decoded on the device: entropy decoding a lane per restart interval, the
+#                        inverse transform, chroma upsampling and colour (default flags: integer code; jpeg_decode.h
+#                        holds its serial routines, which tools/jpeg_decode_rehearse.cpp runs on the host)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -101,6 +104,8 @@ p21=$!
 p22=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/jpeg_encode.hip" -o "$TMP/jpeg_encode.o" &
 p23=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/jpeg_decode.hip" -o "$TMP/jpeg_decode.o" &
+p24=$!
 wait $p1
 wait $p2
 wait $p3
@@ -124,5 +129,6 @@ wait $p20
 wait $p21
 wait $p22
 wait $p23
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" "$TMP/jpeg_encode.o" -o "$OUT"
+wait $p24
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" "$TMP/jpeg_encode.o" "$TMP/jpeg_decode.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

@@ -110,6 +110,29 @@ def read_codes(path, recipe):
   return np.ascontiguousarray(codes)
 
 
+class JpegFile(object):
+  """The bytes of a baseline JPEG file and its plan (``jpeg_decode.parse``), standing in for the file's codes in a chunk
+  of ``build_pack(..., device_jpeg=True)``: ``_flush`` decodes them on the device.  shape and dtype
+  are those of the codes PIL would have made."""
+
+  def __init__(self, path, data, plan):
+    self.path, self.data, self.plan = path, data, plan
+    self.shape, self.dtype = (plan.h, plan.w, 3), np.dtype(np.uint8)
+
+
+def read_jpeg_file(path):
+  """-> ``JpegFile`` of a ``.jpg`` / ``.jpeg`` path whose file the device decoder takes, else None (the PIL path)."""
+  from . import jpeg_decode
+  if not jpeg_decode.is_jpeg_path(path):
+    return None
+  with open(path, 'rb') as f:
+    data = f.read()
+  try:
+    return JpegFile(path, data, jpeg_decode.parse(data))
+  except jpeg_decode.UnsupportedJpeg:
+    return None
+
+
 def draw_windows(rng, recipe, h, w, main_size=80, crop_size=64, augmentation_factor=4):
   """One image's draws -> (windows [(y0, x0, side)], pre-cut records [(oy, ox, flip)] of the resized square or None)."""
   side = min(h, w)
@@ -152,12 +175,18 @@ def pack_shape(recipe, n, main_size=80, crop_size=64, augmentation_factor=4):
 
 def _flush(chunk, recipe, master, row, dev, out_dtype, main_size):
   """Decode, resize (and for ``folder`` pre-cut) one chunk into master[row:]; -> the next row."""
-  groups = {}
+  groups, on_device = {}, {}
+  jpegs = [k for k, (codes, _wins, _cuts) in enumerate(chunk) if isinstance(codes, JpegFile)]
+  if jpegs:  # the chunk's JPEG files in one call: their codes never visit the host
+    from . import jpeg_decode
+    made, _ = jpeg_decode.decode_jpeg_batch([chunk[k][0].data for k in jpegs], dev, plans=[chunk[k][0].plan for k in jpegs],
+                                            names=[chunk[k][0].path for k in jpegs])
+    on_device = dict(zip(jpegs, made))
   for k, (codes, _wins, _cuts) in enumerate(chunk):
     groups.setdefault((codes.dtype.itemsize * 8, codes.shape[2]), []).append(k)
   lin = [None] * len(chunk)
   for (bits, _c), idx in groups.items():
-    cs = [torch.from_numpy(chunk[k][0]).to(dev) for k in idx]
+    cs = [on_device[k] if k in on_device else torch.from_numpy(chunk[k][0]).to(dev) for k in idx]
     ys = [torch.empty((c.shape[0], c.shape[1], 3), dtype=torch.float32, device=dev) for c in cs]
     _cabi.decode_ragged(cs, torch.from_numpy(recipe_table(recipe, bits)).to(dev), 0, ys)
     for k, y in zip(idx, ys):
@@ -176,10 +205,13 @@ def _flush(chunk, recipe, master, row, dev, out_dtype, main_size):
 
 
 def build_pack(paths, recipe, out_dtype, device, seed, main_size=80, crop_size=64, augmentation_factor=4,
-               max_images=MAX_IMAGES, max_bytes=MAX_BYTES, timings=None):
+               max_images=MAX_IMAGES, max_bytes=MAX_BYTES, timings=None, device_jpeg=False):
   """The master pack of ``paths`` (in this order) under ``recipe`` as a device tensor of ``out_dtype``.  Files are read
   one by one and processed in chunks (``plan_chunks``).  ``timings``: a dict that receives the seconds spent reading
-  files ('read') and in the rest ('device', synchronised)."""
+  files ('read') and in the rest ('device', synchronised).  ``device_jpeg`` (the ``folder`` recipe): a baseline JPEG
+  file is read as bytes and parsed only ('read' is then the file reads plus parsing), and every chunk's JPEGs are
+  decoded on the device in one call; the sizes come from the header, so the same random numbers are drawn and the
+  pack is bit for bit the host-decode pack."""
   import time
   if recipe not in RECIPES:
     raise DatasetError('recipe must be one of %s, got %r' % (RECIPES, recipe))
@@ -193,7 +225,9 @@ def build_pack(paths, recipe, out_dtype, device, seed, main_size=80, crop_size=6
   chunk, acc, row = [], 0, 0
   for path in paths:
     t0 = time.perf_counter()
-    codes = read_codes(path, recipe)
+    codes = read_jpeg_file(path) if device_jpeg and recipe == 'folder' else None
+    if codes is None:
+      codes = read_codes(path, recipe)
     t_read += time.perf_counter() - t0
     h, w = codes.shape[:2]
     if min(h, w) < main_size:
@@ -253,8 +287,9 @@ def load_pack(folder):
   return np.load(ppath), man
 
 
-def cached_pack(folder, recipe, out_dtype, device, seed, fold=None, read_limit=-1, cache=None, **sizes):
-  """``build_pack`` of a folder's selection, through the cache directory ``cache`` when given -> (master, hit)."""
+def cached_pack(folder, recipe, out_dtype, device, seed, fold=None, read_limit=-1, cache=None, device_jpeg=False, **sizes):
+  """``build_pack`` of a folder's selection, through the cache directory ``cache`` when given -> (master, hit).
+  ``device_jpeg`` is ``build_pack``'s; the pack is the same either way, so it is no part of the manifest."""
   paths = list_files(folder, fold, read_limit)
   if not paths:
     raise DatasetError('%s: no files selected' % folder)
@@ -263,7 +298,7 @@ def cached_pack(folder, recipe, out_dtype, device, seed, fold=None, read_limit=-
     got = load_pack(cache)
     if got is not None and got[1] == man:
       return torch.from_numpy(got[0]).to(device), True
-  master = build_pack(paths, recipe, out_dtype, device, seed, **sizes)
+  master = build_pack(paths, recipe, out_dtype, device, seed, device_jpeg=device_jpeg, **sizes)
   if cache is not None:
     save_pack(cache, master, man)
   return master, False

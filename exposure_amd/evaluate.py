@@ -12,8 +12,10 @@ outputs of ``net.py:825-877`` the CLI writes the linear result (.npy) and, with 
 ``retouched`` / ``input_tone_mapped`` pictures; with ``--step-by-step`` also the ``intermediateNN`` pictures of
 ``net.py:820-823`` (``evaluate.py:31``); the debug pickle and the cv2-drawn ``steps`` panel are out of scope.
 ``--tiff16`` writes the pictures as 16-bit TIFFs instead, the depth the input files have; ``--device-jpeg-encode``
-writes them as baseline JPEG files encoded on the GPU (``encode_jpeg_batch``).
+writes them as baseline JPEG files encoded on the GPU (``encode_jpeg_batch``); ``--device-jpeg-decode`` decodes
+baseline JPEG inputs on the GPU from the files' bytes (``load_raws``, ``jpeg_decode.py``).
 """
+import sys
 import warnings
 
 import numpy as np
@@ -521,6 +523,36 @@ def load_raw(path):
   return np.asarray(pil.convert('RGB')), 'srgb8'
 
 
+def load_raws(paths, device=None, device_jpeg=False):
+  """``load_raw`` of every path.  With ``device_jpeg`` every ``.jpg`` / ``.jpeg`` path that
+  ``jpeg_decode.parse`` accepts is read as bytes and decoded on ``device`` in one batch call: its codes are an
+  (H, W, 3) uint8 device tensor, bit for bit ``load_raw``'s array, kind 'srgb8', and never visit the host.  Every other
+  path goes through ``load_raw``; one line on stderr names those files and why."""
+  if not device_jpeg:
+    return [load_raw(path) for path in paths]
+  from . import jpeg_decode
+  raws, datas, plans, where, fell = [None] * len(paths), [], [], [], []
+  for i, path in enumerate(paths):
+    if not jpeg_decode.is_jpeg_path(path):
+      fell.append('%s (not a .jpg / .jpeg path)' % path)
+      continue
+    with open(path, 'rb') as f:
+      data = f.read()
+    try:
+      plans.append(jpeg_decode.parse(data))
+    except jpeg_decode.UnsupportedJpeg as e:
+      fell.append('%s (%s)' % (path, e))
+      continue
+    datas.append(data)
+    where.append(i)
+  if fell:
+    print('--device-jpeg-decode: decoded on the host: ' + ', '.join(fell), file=sys.stderr)
+  codes, _ = jpeg_decode.decode_jpeg_batch(datas, device, plans=plans, names=[paths[i] for i in where])
+  for i, c in zip(where, codes):
+    raws[i] = (c, 'srgb8')
+  return [load_raw(path) if raw is None else raw for path, raw in zip(paths, raws)]
+
+
 _DECODE_TABLES = {}
 
 
@@ -543,7 +575,10 @@ def decode_table(kind, device):
 
 
 def upload_codes(codes, device):
-  """The codes of one ``load_raw`` result on the device, as they are (PIL's arrays are read-only: they are only read)."""
+  """The codes of one ``load_raw`` result on the device, as they are (PIL's arrays are read-only: they are only read).
+  Codes that are on a device already (``load_raws`` with ``device_jpeg``) pass through."""
+  if isinstance(codes, torch.Tensor):
+    return codes
   with warnings.catch_warnings():
     warnings.simplefilter('ignore', UserWarning)
     return torch.from_numpy(np.ascontiguousarray(codes)).to(device)
@@ -945,6 +980,10 @@ def main(argv=None):
   ap.add_argument('--device-decode', action='store_true',
                   help='read the images as integer codes (load_raw) and linearise them on the GPU, one ragged call per '
                   'group of --batch images (decode_images): the same tensors as the default host decode')
+  ap.add_argument('--device-jpeg-decode', action='store_true',
+                  help='decode baseline JPEG inputs on the device from the bytes of the files (DESIGN.md 3.35): the same '
+                  'codes as PIL, bit for bit, so every output is byte-identical; a file the device decoder does not '
+                  'take (progressive, CMYK, not a .jpg) goes through PIL and is named on stderr.  Implies --device-decode')
   ap.add_argument('--device-proxy', action='store_true',
                   help="make the agent's 64x64 proxies with one HIP launch per group of --batch images "
                   '(make_low_res_batch) instead of torch\'s interpolate per image.  Same definition, every float32 '
@@ -1056,7 +1095,7 @@ def main(argv=None):
                'one, and the tone-mapped picture needs the float input'
                % ('--fused-decode-curves' if args.fused_decode_curves else '--fused-decode'))
     args.device_decode = args.device_proxy = True
-  if args.device_input_png:
+  if args.device_input_png or args.device_jpeg_decode:
     args.device_decode = True
   if args.pictures_only and not (args.device_png or args.tiff16):
     ap.error('--pictures-only needs --device-png, --tiff16 or --score: it writes the pictures the device makes')
@@ -1163,7 +1202,7 @@ def main(argv=None):
   def load_group(paths):
     """-> the images, and per image its device-made input pictures (None without --device-input-png)"""
     if args.device_decode:
-      raws = [load_raw(path) for path in paths]
+      raws = load_raws(paths, dev, args.device_jpeg_decode)
       if args.device_input_png and show:  # the codes go up once, for the decode and for the input pictures
         staged = list(stage_raws(raws, dt, dev))
         return decode_images(raws, dt, dev, staged), input_pictures(raws, staged)
@@ -1181,7 +1220,7 @@ def main(argv=None):
   if args.fused_decode:  # also with --batch 1: groups of one image
     for b in range(0, len(args.images), args.batch):
       paths = args.images[b:b + args.batch]
-      raws = [load_raw(path) for path in paths]
+      raws = load_raws(paths, dev, args.device_jpeg_decode)
       staged = list(stage_raws(raws, dt, dev))  # the codes go up once, for the pass and for the input pictures
       res = retouch_batch_raw(agent, raws, dt, dev, return_trace='full', intermediates=inter_kind, picture=picture,
                               outputs=not args.pictures_only, staged=staged, curves=curves)

@@ -52,6 +52,9 @@ def parse_args(argv=None):
   ap.add_argument('--real-list', default=None, help='fold file selecting --real-dir files (1-based indices)')
   ap.add_argument('--read-limit', type=int, default=-1, help='read at most this many files of each folder')
   ap.add_argument('--pack-cache', default=None, metavar='DIR', help='keep the built packs under DIR/fake and DIR/real')
+  ap.add_argument('--device-jpeg-decode', action='store_true',
+                  help="decode the folder recipe's baseline JPEG files on the device from their bytes (DESIGN.md 3.35): "
+                  'the same pack, bit for bit; other files go through PIL as before')
   args = ap.parse_args(argv)
   if args.curve_steps is not None and not 1 <= args.curve_steps <= 16:
     ap.error('--curve-steps must be in 1..16')
@@ -80,7 +83,8 @@ def photo_providers(args, cfg, dev, dt):
     folder, recipe, fold = getattr(args, role + '_dir'), getattr(args, role + '_recipe'), getattr(args, role + '_list')
     cache = os.path.join(args.pack_cache, role) if args.pack_cache else None
     t0 = time.time()
-    master, hit = cached_pack(folder, recipe, dt, dev, args.seed + k, fold=fold, read_limit=args.read_limit, cache=cache)
+    master, hit = cached_pack(folder, recipe, dt, dev, args.seed + k, fold=fold, read_limit=args.read_limit, cache=cache,
+                              device_jpeg=args.device_jpeg_decode)
     print('%s pack: %d rows of %d x %d from %s (%s recipe, %s, %.1f s)' %
           (role, master.shape[0], master.shape[1], master.shape[2], folder, recipe,
            'cache hit' if hit else 'built', time.time() - t0))

@@ -63,7 +63,8 @@ extern "C" {
                               expo_chain_fused_curves_fwd_ragged_codes, expo_png_segment_bytes,
                               expo_png_encode_bound, expo_png_encode_workspace_bytes, expo_png_encode_ragged,
                               expo_jpeg_restart_mcus, expo_jpeg_encode_bound, expo_jpeg_encode_workspace_bytes,
-                              expo_jpeg_encode_ragged */
+                              expo_jpeg_encode_ragged, expo_jpeg_decode_plan_bytes, expo_jpeg_decode_workspace_bytes,
+                              expo_jpeg_decode_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -627,6 +628,59 @@ size_t expo_jpeg_encode_workspace_bytes(const int* hs, const int* ws, int n, int
 int expo_jpeg_encode_ragged(const void* const* pics, const int* hs, const int* ws, int n, int quality, int subsampling,
                             void* const* outs, const int64_t* out_capacity, int64_t* sizes, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/*
+ * Baseline JPEG input files decoded on the device (jpeg_decode.hip): the (H, W, 3) uint8 codes that the
+ * reference's readers hand to the network (net.py:739; folder_data_provider.py's cv2.imread), bit for bit what PIL's
+ * open + convert('RGB') makes of the file, without a host codec.  Added exports of ABI 9 (the version is unchanged).
+ *
+ * The picture (DESIGN.md §3.35 fixes every value): T.81 §F.2.2 entropy decoding with any table of up to 256 symbols and
+ * code lengths 1..16, DC predictors 0 at the start of every restart interval; d = coefficient * Q; libjpeg's "islow"
+ * inverse transform with 13-bit constants (columns with descale shift 11, rows with 18, + 128, clamped), in wrapping
+ * int32; component planes of their real samples; libjpeg's triangle-filter chroma upsampling with indices clamped to
+ * the real plane; the JFIF integer colour matrix in 16-bit fixed point.  sampling is PIL's number: 0 = 4:4:4 (Y 1 x 1),
+ * 1 = 4:2:2 (Y 2 x 1), 2 = 4:2:0 (Y 2 x 2), Cb and Cr 1 x 1; ncomps 1 (grey, sampling 0, Y replicated) or 3.  A segment
+ * is a restart interval (a file without DRI is one segment).
+ *
+ * The plan of a picture is a device blob the host builds from the file's header (exposure_amd/jpeg_decode.py: parse),
+ * little endian, 16-byte aligned:
+ *   0     int32 ri            MCUs per restart interval, 0 without DRI
+ *   4     uint8 tq[4], 8 uint8 td[4], 12 uint8 ta[4]   per component its quantiser, DC and AC table
+ *   16    uint8 q[4][64]      the quantiser tables, natural order
+ *   272   4 x 384 bytes       the Huffman tables DC 0, DC 1, AC 0, AC 1, each uint32 limit[16] (limit[l - 1] =
+ *                             (MAXCODE(l) + 1) << (16 - l); for a length without codes the limit before it, 0 before the
+ *                             first), int32 offs[16] (VALPTR(l) - MINCODE(l)), uint8 vals[256] (HUFFVAL)
+ *   1808  int32 seg[nsegs][2] the byte range [begin, end) of every segment's stuffed bytes in the file
+ * The kernels trust none of it for addressing: every read is clamped to the file's length, every write to the lane's
+ * own blocks, every loop is bounded by the geometry given here on the host.
+ *
+ * expo_jpeg_decode_plan_bytes (net.py:739; folder_data_provider.py's cv2.imread): 1808 + 8 nsegs rounded up to 16; 0
+ *   for nsegs < 1.
+ * expo_jpeg_decode_workspace_bytes (net.py:739; folder_data_provider.py's cv2.imread): the scratch a call on these n
+ *   pictures needs (0 for invalid arguments): per picture of a launch group 128 bytes per block and its component planes
+ *   (real rows of whole blocks across), each piece rounded up to 16; the largest launch group's sum.
+ * expo_jpeg_decode_ragged (net.py:739; folder_data_provider.py's cv2.imread):
+ *   files        HOST array of n device pointers to the files' bytes, any alignment; file_bytes HOST [n], 0..2^31-1.
+ *   plans        HOST array of n device pointers to the plans, 16-byte aligned, expo_jpeg_decode_plan_bytes(nsegs[i]) bytes.
+ *   hs, ws, samplings, ncomps, nsegs   HOST [n]: the geometry from the file's header; nsegs[i] = ceil(mcus / Ri).
+ *   outs         HOST array of n device pointers, picture i contiguous [hs[i]][ws[i]][3] uint8 RGB, any alignment.
+ *   status       DEVICE int32 [n], written for every picture: 0, or an OR of 1 (TRUNCATED: a segment consumed more bits
+ *                than it has), 2 (BAD_CODE: 16 bits matched no code, or a DC category above 15) and 4 (BAD_RUN: a run
+ *                stepped past coefficient 63).  On an error the lane stops and the rest of its segment's blocks are
+ *                all-zero coefficients; the picture's pixels are unspecified; its other segments still decode.
+ *   workspace    caller-owned, 16-byte aligned device scratch of at least expo_jpeg_decode_workspace_bytes(...) bytes;
+ *                needs no initialisation and carries no state.
+ * Allocates nothing, does not synchronise with the host, can be captured.  One memset node for `status`, then three
+ * launches per group of 64 pictures, more as further groups on `stream`.  Everything is validated before anything is
+ * enqueued (EXPO_E_BADARG: n < 0, h or w outside 1..65535, a sampling other than 0, 1 and 2, ncomps other than 1 and 3
+ * or grey with a sampling other than 0, nsegs that is ceil(mcus / Ri) for no Ri >= 1, file_bytes outside 0..2^31-1, a
+ * misaligned plan, a workspace that is too small or misaligned, null pointers); n == 0 is a no-op.
+ */
+size_t expo_jpeg_decode_plan_bytes(int nsegs);
+size_t expo_jpeg_decode_workspace_bytes(const int* hs, const int* ws, const int* samplings, const int* ncomps, int n);
+int expo_jpeg_decode_ragged(const void* const* files, const int64_t* file_bytes, const void* const* plans, const int* hs,
+                            const int* ws, const int* samplings, const int* ncomps, const int* nsegs, int n,
+                            void* const* outs, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of
