@@ -130,6 +130,11 @@ SIGNATURES = {
     'expo_jpeg_decode_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_vp), ctypes.POINTER(_i),
                                     ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i,
                                     ctypes.POINTER(_vp), _vp, _vp, _sz, _vp]),
+    'expo_jpeg_decode_sync_workspace_bytes': (_sz, [ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                                                    ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    'expo_jpeg_decode_sync_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_vp), ctypes.POINTER(_i),
+                                         ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                                         ctypes.POINTER(_i), _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp, _sz, _vp]),
     'expo_area_resize_ragged': (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i,
                                      ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp]),
     'expo_pack_recut': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -1266,6 +1271,63 @@ def jpeg_decode_ragged(files, plans, hs, ws, samplings, ncomps, nsegs, outs, sta
                                        hsa, wsa, sa, ca, arr(nsegs), n, _ptr_array(outs), _ptr(status), _ptr(workspace),
                                        workspace.numel() * workspace.element_size(), _stream()),
            'expo_jpeg_decode_ragged')
+
+
+def jpeg_decode_sync_workspace_bytes(hs, ws, samplings, ncomps, nsegs, nsubs):
+  """``expo_jpeg_decode_sync_workspace_bytes``: the scratch of a call of ``jpeg_decode_sync_ragged`` on these files (0 for
+  invalid arguments)."""
+  n = len(hs)
+  arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+  return int(load().expo_jpeg_decode_sync_workspace_bytes(arr(hs), arr(ws), arr(samplings), arr(ncomps), arr(nsegs), arr(nsubs), n))
+
+
+def jpeg_decode_sync_ragged(files, plans, hs, ws, samplings, ncomps, nsegs, nsubs, sub_bytes, grid_rounds, outs, status,
+                            info=None, workspace=None):
+  """``expo_jpeg_decode_sync_ragged``: ``jpeg_decode_ragged`` with the entropy walk of every file without restart markers
+  spread over a lane per subsequence of ``sub_bytes`` file bytes.  nsubs: per file
+  ``Plan.nsubs(sub_bytes)``; grid_rounds: 0..16 further settle launches; info: None or a contiguous int32 device tensor
+  (N,), written for every picture (0 a lane per segment, 1 verified subsequences, 2 the serial fallback).  The pictures
+  and status words are ``jpeg_decode_ragged``'s."""
+  lib = load()
+  n = len(files)
+  if not (len(plans) == len(hs) == len(ws) == len(samplings) == len(ncomps) == len(nsegs) == len(nsubs) == len(outs) == n):
+    raise ExposureHipError('exposure_amd: files, plans, the geometry, nsubs and outs must have the same length')
+  if n == 0:
+    return
+  if not isinstance(files[0], torch.Tensor) or not files[0].is_cuda:
+    raise ExposureHipError('exposure_amd: files must be tensors on a ROCm device (HIP path only, no CPU fallback)')
+  device = files[0].device
+  for what, seq in (('files', files), ('plans', plans), ('outs', outs)):
+    for i, t in enumerate(seq):
+      if not isinstance(t, torch.Tensor) or t.dtype is not torch.uint8 or t.device != device or not t.is_contiguous() or \
+          t.numel() == 0:
+        raise ExposureHipError('exposure_amd: %s[%d] must be a contiguous, non-empty uint8 tensor on %s' % (what, i, device))
+  for i, (o, h, w) in enumerate(zip(outs, hs, ws)):
+    if o.numel() != int(h) * int(w) * 3:
+      raise ExposureHipError('exposure_amd: outs[%d] must hold %d x %d x 3 bytes' % (i, h, w))
+  for i, (p, k) in enumerate(zip(plans, nsegs)):
+    if p.numel() < jpeg_decode_plan_bytes(k):
+      raise ExposureHipError('exposure_amd: plans[%d] is smaller than the plan of %d segments' % (i, k))
+  for what, t in (('status', status), ('info', info)):
+    if what == 'info' and t is None:
+      continue
+    if not isinstance(t, torch.Tensor) or t.dtype is not torch.int32 or t.device != device or not t.is_contiguous() or \
+        t.numel() != n:
+      raise ExposureHipError('exposure_amd: %s must be a contiguous int32 tensor (%d,) on %s' % (what, n, device))
+  arr = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])
+  hsa, wsa, sa, ca, ga, ua = arr(hs), arr(ws), arr(samplings), arr(ncomps), arr(nsegs), arr(nsubs)
+  with torch.cuda.device(device):
+    need = int(lib.expo_jpeg_decode_sync_workspace_bytes(hsa, wsa, sa, ca, ga, ua, n))
+    if workspace is None:
+      workspace = reserve_workspace(device, need)
+      _order_shared_workspace(device)
+    if not workspace.is_cuda or workspace.device != device or workspace.numel() * workspace.element_size() < need:
+      raise ExposureHipError('exposure_amd: workspace must be a device tensor of at least %d bytes on %s' % (need, device))
+    _check(lib.expo_jpeg_decode_sync_ragged(_ptr_array(files), (ctypes.c_int64 * n)(*[f.numel() for f in files]), _ptr_array(plans),
+                                            hsa, wsa, sa, ca, ga, ua, n, int(sub_bytes), int(grid_rounds), _ptr_array(outs),
+                                            _ptr(status), _ptr(info) if info is not None else None, _ptr(workspace),
+                                            workspace.numel() * workspace.element_size(), _stream()),
+           'expo_jpeg_decode_sync_ragged')
 
 
 def area_resize_ragged(xs, windows, S, out):

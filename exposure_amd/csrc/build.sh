@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libexposure_hip.so for gfx950 in-tree (the .so is git-ignored but travels with gpurun).
 # Fifteen translation units plus chain_fused_curves.hip, the sixteenth, dispatch_curves.hip, the seventeenth, and
-# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second, and jpeg_encode.hip, the twenty-third, and jpeg_decode.hip, the twenty-fourth;
+# chain_fused_curves_codes.hip, the eighteenth, and chain_steps_bwd.hip, the nineteenth, and png_encode.hip, the twentieth, and chain_steps_bwd_rc.hip, the twenty-first, and chain_steps_bwd_seq.hip, the twenty-second, and jpeg_encode.hip, the twenty-third, and jpeg_decode.hip, the twenty-fourth, and jpeg_decode_sync.hip, the twenty-fifth;
 # extra arguments go to every compile step.
 #   exposure_hip.hip     the streaming kernels and the C-ABI (default flags)
 #   chain_steps.hip      several forward steps of expo_chain_fwd in one launch (the flags of exposure_hip.hip: it
@@ -48,6 +48,9 @@
 #   jpeg_decode.hip     baseline JPEG files decoded on the device: entropy decoding a lane per restart interval, the
 #                        inverse transform, chroma upsampling and colour (default flags: integer code; jpeg_decode.h
 #                        holds its serial routines, which tools/jpeg_decode_rehearse.cpp runs on the host)
+#   jpeg_decode_sync.hip  files without restart markers decoded in parallel: speculative walks a lane per subsequence,
+#                        their settling, its verification and the stores (default flags: integer code;
+#                        jpeg_decode_sync.h holds its serial routines, which tools/jpeg_sync_rehearse.cpp runs on the host)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${EXPO_LIB_OUT:-$HERE/../libexposure_hip.so}"
@@ -106,6 +109,8 @@ p22=$!
 p23=$!
 "$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/jpeg_decode.hip" -o "$TMP/jpeg_decode.o" &
 p24=$!
+"$HIPCC" "${FLAGS[@]}" "$@" -c "$HERE/jpeg_decode_sync.hip" -o "$TMP/jpeg_decode_sync.o" &
+p25=$!
 wait $p1
 wait $p2
 wait $p3
@@ -130,5 +135,6 @@ wait $p21
 wait $p22
 wait $p23
 wait $p24
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" "$TMP/jpeg_encode.o" "$TMP/jpeg_decode.o" -o "$OUT"
+wait $p25
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$TMP/exposure_hip.o" "$TMP/chain_fused.o" "$TMP/nn_ops.o" "$TMP/chain_fused_bwd.o" "$TMP/curve_generic.o" "$TMP/conv_ops.o" "$TMP/critic_step.o" "$TMP/decode.o" "$TMP/datasets.o" "$TMP/chain_steps.o" "$TMP/proxy.o" "$TMP/metric.o" "$TMP/chain_fused_codes.o" "$TMP/proxy_codes.o" "$TMP/codes_lut.o" "$TMP/chain_fused_curves.o" "$TMP/dispatch_curves.o" "$TMP/chain_fused_curves_codes.o" "$TMP/chain_steps_bwd.o" "$TMP/png_encode.o" "$TMP/chain_steps_bwd_rc.o" "$TMP/chain_steps_bwd_seq.o" "$TMP/jpeg_encode.o" "$TMP/jpeg_decode.o" "$TMP/jpeg_decode_sync.o" -o "$OUT"
 echo "built $OUT (sources $DIGEST)"

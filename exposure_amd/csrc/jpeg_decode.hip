@@ -187,6 +187,40 @@ int64_t group_workspace(const int* hs, const int* ws, const int* samplings, cons
 
 }  // namespace
 
+// Not exported: the inverse transform and the colour kernel for pictures [base, base + m) (m <= 64) whose parts of the
+// workspace start at bases[0..m), for csrc/jpeg_decode_sync.hip, which fills the coefficients in its own way.  With
+// enqueue false it only checks the grids.
+namespace expo {
+int jpeg_decode_reconstruct(const void* const* plans, const int* hs, const int* ws, const int* samplings, const int* ncomps,
+                            int base, int m, const int64_t* bases, void* const* outs, void* workspace, void* stream, bool enqueue) {
+  DecTable tab = {};
+  tab.n = m;
+  int64_t idct = 0, units = 0;
+  for (int j = 0; j < m; ++j) {
+    const int i = base + j;
+    const jpegdec::Geometry g = jpegdec::geometry(hs[i], ws[i], samplings[i], ncomps[i]);
+    tab.plan[j] = static_cast<const uint8_t*>(plans[i]);
+    tab.out[j] = static_cast<uint8_t*>(outs[i]);
+    tab.base[j] = bases[j];
+    tab.hw[j] = uint32_t(hs[i]) << 16 | uint32_t(ws[i]);
+    tab.mode[j] = uint8_t(samplings[i] | ncomps[i] << 2);
+    if (idct <= INT_MAX) tab.first_idct[j] = int(idct);
+    if (units <= INT_MAX) tab.first_rgb[j] = int(units);
+    idct += (jpegdec::blocks(g) + kIdctBlocks - 1) / kIdctBlocks;
+    units += (int64_t(jpegdec::plane_h(g, g.ncomp - 1)) * jpegdec::plane_w(g, g.ncomp - 1) + kThreads - 1) / kThreads;
+  }
+  if (idct > INT_MAX || units > INT_MAX) return fail(EXPO_E_BADARG, "too many blocks in one launch");
+  if (!enqueue) return EXPO_OK;
+  tab.first_idct[m] = int(idct), tab.first_rgb[m] = int(units);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3(unsigned(idct)), dim3(kThreads), 0, s, tab, static_cast<uint8_t*>(workspace));
+  HIP_TRY(hipGetLastError(), "jpeg_idct launch");
+  hipLaunchKernelGGL(jpeg_rgb_kernel, dim3(unsigned(units)), dim3(kThreads), 0, s, tab, static_cast<const uint8_t*>(workspace));
+  HIP_TRY(hipGetLastError(), "jpeg_rgb launch");
+  return EXPO_OK;
+}
+}  // namespace expo
+
 extern "C" {
 
 size_t expo_jpeg_decode_plan_bytes(int nsegs) { return nsegs < 1 ? 0 : size_t(jpegdec::plan_bytes(nsegs)); }

@@ -173,14 +173,14 @@ def pack_shape(recipe, n, main_size=80, crop_size=64, augmentation_factor=4):
   return (augmentation_factor * n, s, s, 3)
 
 
-def _flush(chunk, recipe, master, row, dev, out_dtype, main_size):
+def _flush(chunk, recipe, master, row, dev, out_dtype, main_size, jpeg_sync='auto'):
   """Decode, resize (and for ``folder`` pre-cut) one chunk into master[row:]; -> the next row."""
   groups, on_device = {}, {}
   jpegs = [k for k, (codes, _wins, _cuts) in enumerate(chunk) if isinstance(codes, JpegFile)]
   if jpegs:  # the chunk's JPEG files in one call: their codes never visit the host
     from . import jpeg_decode
     made, _ = jpeg_decode.decode_jpeg_batch([chunk[k][0].data for k in jpegs], dev, plans=[chunk[k][0].plan for k in jpegs],
-                                            names=[chunk[k][0].path for k in jpegs])
+                                            names=[chunk[k][0].path for k in jpegs], sync=jpeg_sync)
     on_device = dict(zip(jpegs, made))
   for k, (codes, _wins, _cuts) in enumerate(chunk):
     groups.setdefault((codes.dtype.itemsize * 8, codes.shape[2]), []).append(k)
@@ -205,13 +205,14 @@ def _flush(chunk, recipe, master, row, dev, out_dtype, main_size):
 
 
 def build_pack(paths, recipe, out_dtype, device, seed, main_size=80, crop_size=64, augmentation_factor=4,
-               max_images=MAX_IMAGES, max_bytes=MAX_BYTES, timings=None, device_jpeg=False):
+               max_images=MAX_IMAGES, max_bytes=MAX_BYTES, timings=None, device_jpeg=False, jpeg_sync='auto'):
   """The master pack of ``paths`` (in this order) under ``recipe`` as a device tensor of ``out_dtype``.  Files are read
   one by one and processed in chunks (``plan_chunks``).  ``timings``: a dict that receives the seconds spent reading
   files ('read') and in the rest ('device', synchronised).  ``device_jpeg`` (the ``folder`` recipe): a baseline JPEG
   file is read as bytes and parsed only ('read' is then the file reads plus parsing), and every chunk's JPEGs are
   decoded on the device in one call; the sizes come from the header, so the same random numbers are drawn and the
-  pack is bit for bit the host-decode pack."""
+  pack is bit for bit the host-decode pack.  ``jpeg_sync`` is ``decode_jpeg_batch``'s ``sync`` (False: the one-lane
+  entropy walk for files without restart markers, for comparison runs; the pack is the same)."""
   import time
   if recipe not in RECIPES:
     raise DatasetError('recipe must be one of %s, got %r' % (RECIPES, recipe))
@@ -235,7 +236,7 @@ def build_pack(paths, recipe, out_dtype, device, seed, main_size=80, crop_size=6
     b = h * w * 12
     if chunk and (len(chunk) == max_images or acc + b > max_bytes):
       t0 = time.perf_counter()
-      row = _flush(chunk, recipe, master, row, dev, out_dtype, main_size)
+      row = _flush(chunk, recipe, master, row, dev, out_dtype, main_size, jpeg_sync)
       t_dev += time.perf_counter() - t0
       chunk, acc = [], 0
     wins, cuts = draw_windows(rng, recipe, h, w, main_size, crop_size, augmentation_factor)
@@ -243,7 +244,7 @@ def build_pack(paths, recipe, out_dtype, device, seed, main_size=80, crop_size=6
     acc += b
   t0 = time.perf_counter()
   if chunk:
-    row = _flush(chunk, recipe, master, row, dev, out_dtype, main_size)
+    row = _flush(chunk, recipe, master, row, dev, out_dtype, main_size, jpeg_sync)
   if dev.type == 'cuda':
     torch.cuda.synchronize(dev)
   t_dev += time.perf_counter() - t0
@@ -287,9 +288,11 @@ def load_pack(folder):
   return np.load(ppath), man
 
 
-def cached_pack(folder, recipe, out_dtype, device, seed, fold=None, read_limit=-1, cache=None, device_jpeg=False, **sizes):
+def cached_pack(folder, recipe, out_dtype, device, seed, fold=None, read_limit=-1, cache=None, device_jpeg=False,
+                jpeg_sync='auto', **sizes):
   """``build_pack`` of a folder's selection, through the cache directory ``cache`` when given -> (master, hit).
-  ``device_jpeg`` is ``build_pack``'s; the pack is the same either way, so it is no part of the manifest."""
+  ``device_jpeg`` and ``jpeg_sync`` are ``build_pack``'s; the pack is the same either way, so they are no part of the
+  manifest."""
   paths = list_files(folder, fold, read_limit)
   if not paths:
     raise DatasetError('%s: no files selected' % folder)
@@ -298,7 +301,7 @@ def cached_pack(folder, recipe, out_dtype, device, seed, fold=None, read_limit=-
     got = load_pack(cache)
     if got is not None and got[1] == man:
       return torch.from_numpy(got[0]).to(device), True
-  master = build_pack(paths, recipe, out_dtype, device, seed, device_jpeg=device_jpeg, **sizes)
+  master = build_pack(paths, recipe, out_dtype, device, seed, device_jpeg=device_jpeg, jpeg_sync=jpeg_sync, **sizes)
   if cache is not None:
     save_pack(cache, master, man)
   return master, False

@@ -523,7 +523,7 @@ def load_raw(path):
   return np.asarray(pil.convert('RGB')), 'srgb8'
 
 
-def load_raws(paths, device=None, device_jpeg=False):
+def load_raws(paths, device=None, device_jpeg=False, jpeg_sync='auto'):
   """``load_raw`` of every path.  With ``device_jpeg`` every ``.jpg`` / ``.jpeg`` path that
   ``jpeg_decode.parse`` accepts is read as bytes and decoded on ``device`` in one batch call: its codes are an
   (H, W, 3) uint8 device tensor, bit for bit ``load_raw``'s array, kind 'srgb8', and never visit the host.  Every other
@@ -547,7 +547,7 @@ def load_raws(paths, device=None, device_jpeg=False):
     where.append(i)
   if fell:
     print('--device-jpeg-decode: decoded on the host: ' + ', '.join(fell), file=sys.stderr)
-  codes, _ = jpeg_decode.decode_jpeg_batch(datas, device, plans=plans, names=[paths[i] for i in where])
+  codes, _ = jpeg_decode.decode_jpeg_batch(datas, device, plans=plans, names=[paths[i] for i in where], sync=jpeg_sync)
   for i, c in zip(where, codes):
     raws[i] = (c, 'srgb8')
   return [load_raw(path) if raw is None else raw for path, raw in zip(paths, raws)]
@@ -984,6 +984,9 @@ def main(argv=None):
                   help='decode baseline JPEG inputs on the device from the bytes of the files (DESIGN.md 3.35): the same '
                   'codes as PIL, bit for bit, so every output is byte-identical; a file the device decoder does not '
                   'take (progressive, CMYK, not a .jpg) goes through PIL and is named on stderr.  Implies --device-decode')
+  ap.add_argument('--jpeg-serial-entropy', action='store_true',
+                  help='with --device-jpeg-decode: walk a file without restart markers with one lane instead of a lane per '
+                  'subsequence (DESIGN.md 3.36), for comparison runs; the same codes, so every output is byte-identical')
   ap.add_argument('--device-proxy', action='store_true',
                   help="make the agent's 64x64 proxies with one HIP launch per group of --batch images "
                   '(make_low_res_batch) instead of torch\'s interpolate per image.  Same definition, every float32 '
@@ -1202,7 +1205,7 @@ def main(argv=None):
   def load_group(paths):
     """-> the images, and per image its device-made input pictures (None without --device-input-png)"""
     if args.device_decode:
-      raws = load_raws(paths, dev, args.device_jpeg_decode)
+      raws = load_raws(paths, dev, args.device_jpeg_decode, False if args.jpeg_serial_entropy else 'auto')
       if args.device_input_png and show:  # the codes go up once, for the decode and for the input pictures
         staged = list(stage_raws(raws, dt, dev))
         return decode_images(raws, dt, dev, staged), input_pictures(raws, staged)
@@ -1220,7 +1223,7 @@ def main(argv=None):
   if args.fused_decode:  # also with --batch 1: groups of one image
     for b in range(0, len(args.images), args.batch):
       paths = args.images[b:b + args.batch]
-      raws = load_raws(paths, dev, args.device_jpeg_decode)
+      raws = load_raws(paths, dev, args.device_jpeg_decode, False if args.jpeg_serial_entropy else 'auto')
       staged = list(stage_raws(raws, dt, dev))  # the codes go up once, for the pass and for the input pictures
       res = retouch_batch_raw(agent, raws, dt, dev, return_trace='full', intermediates=inter_kind, picture=picture,
                               outputs=not args.pictures_only, staged=staged, curves=curves)

@@ -12,6 +12,9 @@ from . import _cabi
 TRUNCATED, BAD_CODE, BAD_RUN = 1, 2, 4  # the flags of a picture's status word
 STATUS_NAMES = ((TRUNCATED, 'TRUNCATED'), (BAD_CODE, 'BAD_CODE'), (BAD_RUN, 'BAD_RUN'))
 PLAN_HEAD_BYTES = 1808
+SUB_BYTES = 128  # the subsequence of the parallel entropy walk; the fastest of 64..512 on smooth 16 x 512x512 files, not on noise: profiles/jpeg_decode.md
+GRID_ROUNDS = 4  # further settle launches, each carries a state across one more boundary between workgroups; not swept
+SYNC_MIN_BYTES = 4096  # 'auto': a file whose one segment has at least this many bytes takes the parallel walk; not swept (noise-like files lose 0.60x - 0.79x by it)
 MAX_BYTES = 1 << 30  # the workspace of one call (coefficients and planes: 3.5 to 5 bytes per pixel), as datasets.MAX_BYTES
 
 _ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7,
@@ -52,6 +55,18 @@ class Plan(object):
   @property
   def nsegs(self):
     return int(self.segments.shape[0])
+
+  @property
+  def segment_bytes(self):
+    """the bytes of the one segment of a file without restart markers, as the device clamps them; 0 for other files"""
+    if self.nsegs != 1:
+      return 0
+    begin = min(max(int(self.segments[0, 0]), 0), self.nbytes)
+    return min(max(int(self.segments[0, 1]), begin), self.nbytes) - begin
+
+  def nsubs(self, sub_bytes):
+    """the subsequences of ``sub_bytes`` bytes of a file without restart markers (at least one); 1 for other files"""
+    return 1 if self.segment_bytes <= sub_bytes else -(-self.segment_bytes // int(sub_bytes))
 
 
 def _huff_arrays(bits, vals):
@@ -196,20 +211,34 @@ def parse(data):
               segments=segments.astype(np.int32), nbytes=n, mcus=mcus, blob=blob)
 
 
-def workspace_bytes(plans):
-  return _cabi.jpeg_decode_workspace_bytes([p.h for p in plans], [p.w for p in plans], [p.sampling for p in plans],
-                                           [p.ncomp for p in plans])
+def workspace_bytes(plans, sub_bytes=None):
+  """the scratch of one call on these files: the serial call's, or with ``sub_bytes`` the parallel call's"""
+  if sub_bytes is None:
+    return _cabi.jpeg_decode_workspace_bytes([p.h for p in plans], [p.w for p in plans], [p.sampling for p in plans],
+                                             [p.ncomp for p in plans])
+  return _cabi.jpeg_decode_sync_workspace_bytes([p.h for p in plans], [p.w for p in plans], [p.sampling for p in plans],
+                                                [p.ncomp for p in plans], [p.nsegs for p in plans],
+                                                [p.nsubs(sub_bytes) for p in plans])
 
 
-def decode_jpeg_batch(datas, device, errors='raise', plans=None, max_bytes=MAX_BYTES, names=None):
+def decode_jpeg_batch(datas, device, errors='raise', plans=None, max_bytes=MAX_BYTES, names=None, sync='auto',
+                      sub_bytes=SUB_BYTES, grid_rounds=GRID_ROUNDS, sync_min_bytes=SYNC_MIN_BYTES, info=False):
   """the bytes of N baseline JPEG files -> (N contiguous (H, W, 3) uint8 tensors on ``device``, their status words as a
   list of ints).  ``parse`` runs on every file first (``UnsupportedJpeg`` propagates; pass ``plans=`` to reuse earlier
   results), then the files and plans are uploaded in one copy and decoded in as few calls as a workspace of
   ``max_bytes`` allows (a picture that needs more on its own gets a call of its own).  errors='raise': a non-zero
-  status raises ``JpegDataError`` naming the files (``names``, default their indices); 'return': the caller looks."""
+  status raises ``JpegDataError`` naming the files (``names``, default their indices); 'return': the caller looks.
+  sync: True decodes through ``expo_jpeg_decode_sync_ragged`` (a file without restart markers is walked
+  by a lane per subsequence of ``sub_bytes`` bytes, with ``grid_rounds`` further settle launches), False through
+  ``expo_jpeg_decode_ragged`` (a lane per file for such files), 'auto' through the former when a file of the call has
+  one segment of at least ``sync_min_bytes`` bytes; the tensors and status words are the same either way.  info=True
+  also returns the info words as a third list (0 a lane per segment, 1 verified subsequences, 2 the serial fallback;
+  all 0 through the serial call)."""
   import torch
   if errors not in ('raise', 'return'):
     raise ValueError("errors must be 'raise' or 'return'")
+  if sync not in ('auto', True, False):
+    raise ValueError("sync must be 'auto', True or False")
   device = torch.device(device)
   datas = [bytes(x) for x in datas]
   plans = [parse(x) for x in datas] if plans is None else list(plans)
@@ -217,7 +246,9 @@ def decode_jpeg_batch(datas, device, errors='raise', plans=None, max_bytes=MAX_B
     raise ValueError('datas and plans must have the same length')
   n = len(datas)
   if n == 0:
-    return [], []
+    return ([], [], []) if info else ([], [])
+  if sync == 'auto':
+    sync = any(p.nsegs == 1 and p.segment_bytes >= sync_min_bytes for p in plans)
   # one upload: every plan at a multiple of 16 bytes, then the files back to back
   offs, at = [], 0
   for p in plans:
@@ -235,7 +266,8 @@ def decode_jpeg_batch(datas, device, errors='raise', plans=None, max_bytes=MAX_B
   blob = torch.from_numpy(host).to(device)
   outs = [torch.empty((p.h, p.w, 3), dtype=torch.uint8, device=device) for p in plans]
   status = torch.empty((n,), dtype=torch.int32, device=device)
-  each = [workspace_bytes([p]) for p in plans]  # a call's workspace is at most the sum of its pictures'
+  words = torch.zeros((n,), dtype=torch.int32, device=device) if info else None
+  each = [workspace_bytes([p], sub_bytes if sync else None) for p in plans]  # a call's workspace is at most the sum of its pictures'
   start = 0
   while start < n:
     stop, total = start + 1, each[start]
@@ -243,14 +275,18 @@ def decode_jpeg_batch(datas, device, errors='raise', plans=None, max_bytes=MAX_B
       total += each[stop]
       stop += 1
     sel = range(start, stop)
-    _cabi.jpeg_decode_ragged([blob[foffs[i]:foffs[i] + len(datas[i])] for i in sel], [blob[offs[i]:offs[i] + plans[i].blob.size] for i in sel],
-                             [plans[i].h for i in sel], [plans[i].w for i in sel], [plans[i].sampling for i in sel],
-                             [plans[i].ncomp for i in sel], [plans[i].nsegs for i in sel], [outs[i] for i in sel],
-                             status[start:stop])
+    args = ([blob[foffs[i]:foffs[i] + len(datas[i])] for i in sel], [blob[offs[i]:offs[i] + plans[i].blob.size] for i in sel],
+            [plans[i].h for i in sel], [plans[i].w for i in sel], [plans[i].sampling for i in sel],
+            [plans[i].ncomp for i in sel], [plans[i].nsegs for i in sel])
+    if sync:
+      _cabi.jpeg_decode_sync_ragged(*args, [plans[i].nsubs(sub_bytes) for i in sel], sub_bytes, grid_rounds,
+                                    [outs[i] for i in sel], status[start:stop], words[start:stop] if info else None)
+    else:
+      _cabi.jpeg_decode_ragged(*args, [outs[i] for i in sel], status[start:stop])
     start = stop
   statuses = [int(s) for s in status.cpu().tolist()]
   if errors == 'raise' and any(statuses):
     names = list(range(n)) if names is None else list(names)
     raise JpegDataError('JPEG entropy data did not decode: ' +
                         ', '.join('%s (%s)' % (names[i], status_text(s)) for i, s in enumerate(statuses) if s))
-  return outs, statuses
+  return (outs, statuses, [int(v) for v in words.cpu().tolist()]) if info else (outs, statuses)

@@ -55,6 +55,9 @@ def parse_args(argv=None):
   ap.add_argument('--device-jpeg-decode', action='store_true',
                   help="decode the folder recipe's baseline JPEG files on the device from their bytes (DESIGN.md 3.35): "
                   'the same pack, bit for bit; other files go through PIL as before')
+  ap.add_argument('--jpeg-serial-entropy', action='store_true',
+                  help='with --device-jpeg-decode: walk a file without restart markers with one lane instead of a lane per '
+                  'subsequence (DESIGN.md 3.36), for comparison runs; the same pack')
   args = ap.parse_args(argv)
   if args.curve_steps is not None and not 1 <= args.curve_steps <= 16:
     ap.error('--curve-steps must be in 1..16')
@@ -84,7 +87,7 @@ def photo_providers(args, cfg, dev, dt):
     cache = os.path.join(args.pack_cache, role) if args.pack_cache else None
     t0 = time.time()
     master, hit = cached_pack(folder, recipe, dt, dev, args.seed + k, fold=fold, read_limit=args.read_limit, cache=cache,
-                              device_jpeg=args.device_jpeg_decode)
+                              device_jpeg=args.device_jpeg_decode, jpeg_sync=False if args.jpeg_serial_entropy else 'auto')
     print('%s pack: %d rows of %d x %d from %s (%s recipe, %s, %.1f s)' %
           (role, master.shape[0], master.shape[1], master.shape[2], folder, recipe,
            'cache hit' if hit else 'built', time.time() - t0))

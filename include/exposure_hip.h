@@ -64,7 +64,8 @@ extern "C" {
                               expo_png_encode_bound, expo_png_encode_workspace_bytes, expo_png_encode_ragged,
                               expo_jpeg_restart_mcus, expo_jpeg_encode_bound, expo_jpeg_encode_workspace_bytes,
                               expo_jpeg_encode_ragged, expo_jpeg_decode_plan_bytes, expo_jpeg_decode_workspace_bytes,
-                              expo_jpeg_decode_ragged */
+                              expo_jpeg_decode_ragged, expo_jpeg_decode_sync_workspace_bytes,
+                              expo_jpeg_decode_sync_ragged */
 
 #define EXPO_OK 0
 #define EXPO_E_BADARG (-1)
@@ -681,6 +682,48 @@ size_t expo_jpeg_decode_workspace_bytes(const int* hs, const int* ws, const int*
 int expo_jpeg_decode_ragged(const void* const* files, const int64_t* file_bytes, const void* const* plans, const int* hs,
                             const int* ws, const int* samplings, const int* ncomps, const int* nsegs, int n,
                             void* const* outs, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Baseline JPEG files without restart markers decoded in parallel on the device (jpeg_decode_sync.hip):
+ * the pictures and status words of expo_jpeg_decode_ragged, for every input, with the entropy walk of a one-segment
+ * file spread over a lane per subsequence.  Added exports of ABI 9 (the version is unchanged).
+ *
+ * Subsequence i of the segment [begin, end) of a file without DRI is its bytes [begin + i sub_bytes, min(begin + (i + 1)
+ * sub_bytes, end)).  Every subsequence is walked from a speculative entry state (bit offset, block in the MCU,
+ * coefficient index); the lanes then take the exit of the subsequence before them as their entry and walk again until
+ * nothing changes (rounds inside a workgroup of 256 subsequences, then grid_rounds further launches that carry the last
+ * exit of a workgroup to the next).  The chain in[0] = the exact start, in[i] = out[i - 1] is verified on the device;
+ * a verified picture's coefficients are stored by a second walk, a picture whose chain is not verified is decoded by the
+ * one-lane walk of expo_jpeg_decode_ragged inside the same call.
+ *
+ * expo_jpeg_decode_sync_workspace_bytes (net.py:739; folder_data_provider.py's cv2.imread): the scratch a call on these n
+ *   pictures needs (0 for invalid arguments): expo_jpeg_decode_workspace_bytes' layout per launch group, then per
+ *   picture with nsegs 1 and nsubs > 1 two state words, a 16-byte payload and 16 bytes of first block and predictors per
+ *   subsequence, two boundary words per 256 subsequences and 16 bytes of results, each piece rounded up to 16.
+ * expo_jpeg_decode_sync_ragged (net.py:739; folder_data_provider.py's cv2.imread): the arguments of
+ *   expo_jpeg_decode_ragged, and
+ *   nsubs        HOST [n]: max(1, ceil(bytes of the segment / sub_bytes)) of a picture with nsegs 1, and 1 for the others.
+ *                The device clamps to the segment: a wrong count addresses nothing outside the file or the workspace, and
+ *                its picture is decoded by the one-lane walk.
+ *   sub_bytes    a multiple of 16 in 32..65536.
+ *   grid_rounds  0..16: the settle launch runs once and then grid_rounds times more.
+ *   info         DEVICE int32 [n] or null, written for every picture: 0 a lane per segment (restart intervals, or one
+ *                subsequence), 1 decoded through verified subsequences, 2 the chain was not verified and the serial lane
+ *                decoded it.
+ * outs and status are expo_jpeg_decode_ragged's for every file whose segment has a 00 behind every FF (every plan the
+ * host parser makes).  Allocates nothing, does not synchronise with the host, can be captured.  A memset node each for
+ * `status` and `info`, then per group of 64 pictures 1 + grid_rounds settle launches, the scan, a memset node over the
+ * sync pictures' coefficients, the emit, the serial launch and the two reconstruction launches.  The workspace needs no
+ * initialisation and carries no state.  Everything is validated before anything is enqueued (EXPO_E_BADARG: the cases of
+ * expo_jpeg_decode_ragged, sub_bytes that is no multiple of 16 in 32..65536, grid_rounds outside 0..16, nsubs outside
+ * 1..2^26, nsubs other than 1 for a picture with nsegs > 1); n == 0 is a no-op.
+ */
+size_t expo_jpeg_decode_sync_workspace_bytes(const int* hs, const int* ws, const int* samplings, const int* ncomps,
+                                             const int* nsegs, const int* nsubs, int n);
+int expo_jpeg_decode_sync_ragged(const void* const* files, const int64_t* file_bytes, const void* const* plans, const int* hs,
+                                 const int* ws, const int* samplings, const int* ncomps, const int* nsegs, const int* nsubs,
+                                 int n, int sub_bytes, int grid_rounds, void* const* outs, int32_t* status, int32_t* info,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Training sets (datasets.hip): the master pack of a folder of photos and its per-epoch re-cut.  Added exports of

@@ -1,15 +1,20 @@
-"""Timing of the device JPEG decoder (DESIGN.md §3.35), by the method of tools/bench_jpeg_encode.py.
+"""Timing of the device JPEG decoder (DESIGN.md §3.35, §3.36), by the method of tools/bench_jpeg_encode.py.
 
 Pictures: synthetic uint8 pictures made on the host, independent noise per pixel (the worst case of a transform coder)
 and "smooth" (noise of 1/8 the size enlarged bilinearly, a stand-in for a photograph's local smoothness); neither is a
-photograph.  16 x 512x512 (sixteen pictures), 1 x 4000x6000 and 16 x 4000x6000 (one picture's file sixteen times).  Each
+photograph, and the tree holds none: "smooth" is the most photograph-like picture there is and stands in for them.  16 x 512x512 (sixteen pictures), 1 x 4000x6000 and 16 x 4000x6000 (one picture's file sixteen times).  Each
 picture at --quality in 4:2:0 and 4:4:4, as two files:
   own   this project's device encoder (expo_jpeg_encode_ragged): restart intervals of 8 / 16 MCUs, a lane per interval
-  pil   PIL's save(..., 'JPEG'): no restart markers, so ONE lane walks the whole file
+  pil   PIL's save(..., 'JPEG'): no restart markers.  These rows go through expo_jpeg_decode_sync_ragged (§3.36: a lane
+        per subsequence of jpeg_decode.SUB_BYTES bytes, jpeg_decode.GRID_ROUNDS further settle launches) and carry the
+        info words (how many pictures went which way), the one-lane walk of expo_jpeg_decode_ragged on the same files
+        (what --jpeg-serial-entropy runs; measured once when it takes more than --slow-ms), and the sweep of sub_bytes
+        over 64, 128, 256 and 512
 Per case:
   device ms per expo_jpeg_decode_ragged call from events (warm-up, --reps calls, median / min / max of --rounds; a call
     of more than --slow-ms is measured once, and the row says so), as a multiple of a device copy of the output bytes;
-    the three kernels' shares from torch.profiler, one profiled call (where the profiler is available);
+    the kernels' shares (settle, scan, emit, serial or entropy, idct, rgb) from torch.profiler, one profiled call
+    (where the profiler is available);
   file bytes -> device codes: jpeg_decode.decode_jpeg_batch (parse, one upload, the call), host clock around a
     synchronise;
   PIL: Image.open + convert('RGB') + upload of the same files, alternating in the same process, host clock.
@@ -74,7 +79,7 @@ def kernel_shares(fn):
       torch.cuda.synchronize()
     out = {}
     for e in prof.key_averages():
-      for k in ('entropy', 'idct', 'rgb'):
+      for k in ('sync_settle', 'sync_scan', 'sync_emit', 'sync_serial', 'entropy', 'idct', 'rgb'):
         if 'jpeg_%s_kernel' % k in e.key:
           out[k] = out.get(k, 0.0) + getattr(e, 'device_time_total', getattr(e, 'cuda_time_total', 0.0)) / 1e3
     return out or None
@@ -83,17 +88,45 @@ def kernel_shares(fn):
 
 
 def case(name, kind, sub, datas, args, dev):
+  """one row; a 'pil' row is the §3.36 entry with the one-lane path, the info words and the sweep beside it"""
   plans = [jpeg_decode.parse(d) for d in datas]
   files = [torch.frombuffer(bytearray(d), dtype=torch.uint8).to(dev) for d in datas]
   blobs = [torch.from_numpy(p.blob).to(dev) for p in plans]
   outs = [torch.empty((p.h, p.w, 3), dtype=torch.uint8, device=dev) for p in plans]
   status = torch.empty((len(datas),), dtype=torch.int32, device=dev)
   geo = ([p.h for p in plans], [p.w for p in plans], [p.sampling for p in plans], [p.ncomp for p in plans], [p.nsegs for p in plans])
-  call = lambda: _cabi.jpeg_decode_ragged(files, blobs, *geo, outs, status)
-  _cabi.reserve_workspace(dev, jpeg_decode.workspace_bytes(plans))  # (so that the first call allocates nothing)
+  serial_call = lambda: _cabi.jpeg_decode_ragged(files, blobs, *geo, outs, status)
+  info = torch.zeros((len(datas),), dtype=torch.int32, device=dev)
+  sync_call = lambda b: _cabi.jpeg_decode_sync_ragged(files, blobs, *geo, [p.nsubs(b) for p in plans], b, jpeg_decode.GRID_ROUNDS,
+                                                      outs, status, info)
+  sync = kind == 'pil'
+  call = (lambda: sync_call(jpeg_decode.SUB_BYTES)) if sync else serial_call
+  _cabi.reserve_workspace(dev, max(jpeg_decode.workspace_bytes(plans), jpeg_decode.workspace_bytes(plans, 64)))  # (the first call allocates nothing)
   torch.cuda.synchronize()
   first = timed(call, 1)
   assert status.cpu().tolist() == [0] * len(datas)
+  words = info.cpu().tolist()
+  extra = {}
+  if sync:
+    keep = [o.clone() for o in outs]
+    once = timed(serial_call, 1)  # the parent's one-lane path on the same files, in the same process
+    print('  %s %s parallel %.1f ms, one lane %.1f ms' % (name, sub, first, once), file=sys.stderr, flush=True)
+    assert all(torch.equal(a, b) for a, b in zip(keep, outs))
+    reps = max(1, min(args.reps, int(args.slow_ms / max(once, 1e-3))))
+    extra['serial_ms'] = dict(median=once, min=once, max=once) if once > args.slow_ms else rounds_ms(serial_call, args.rounds, reps)
+    extra['serial_measured'] = 'once' if once > args.slow_ms else '%d x %d' % (args.rounds, reps)
+    extra['info'] = {str(v): words.count(v) for v in (0, 1, 2)}
+    sweep = {}
+    for b in (64, 128, 256, 512):
+      t = timed(lambda: sync_call(b), 1)
+      print('  %s %s sub_bytes %d: %.1f ms' % (name, sub, b, t), file=sys.stderr, flush=True)  # (a slow row stays audible)
+      got = info.cpu().tolist()
+      assert all(torch.equal(a, c) for a, c in zip(keep, outs))
+      reps = max(1, min(args.reps, int(args.slow_ms / max(t, 1e-3))))
+      ms = dict(median=t, min=t, max=t) if t > args.slow_ms else rounds_ms(lambda: sync_call(b), args.rounds, reps)
+      sweep[str(b)] = dict(ms=ms['median'], info={str(v): got.count(v) for v in (0, 1, 2)})
+    extra['sweep'] = sweep
+    del keep
   if first > args.slow_ms:  # seconds per call: this one call is the measurement
     dec, measured = dict(median=first, min=first, max=first), 'once'
   else:
@@ -125,7 +158,7 @@ def case(name, kind, sub, datas, args, dev):
   row = dict(case=name, files=kind, subsampling=sub, images=len(datas), file_bytes=sum(len(d) for d in datas),
              out_bytes=sum(o.numel() for o in outs), segments=sum(p.nsegs for p in plans), device_ms=dec, measured=measured,
              kernels_ms=shares, copy_ms=cp, of_copy=dec['median'] / cp['median'], from_file_bytes_ms=statistics.median(e2e),
-             pil_ms=statistics.median(pil), speedup_vs_pil=statistics.median(pil) / statistics.median(e2e))
+             pil_ms=statistics.median(pil), speedup_vs_pil=statistics.median(pil) / statistics.median(e2e), **extra)
   print(json.dumps(row), flush=True)
   return row
 
@@ -155,14 +188,29 @@ def pack_case(n, args, dev):
 
 
 def markdown(rows, pack):
-  out = ['| pictures | files | sampling | segments | device ms (min - max) | measured | entropy / idct / rgb ms | x copy | '
+  out = ['| pictures | files | sampling | segments | device ms (min - max) | measured | settle / scan / emit / serial (entropy) / idct / rgb ms | x copy | '
          'file bytes to device codes ms | PIL open + convert + upload ms | vs PIL |', '|---|---|---|---|---|---|---|---|---|---|---|']
   for r in rows:
     d, k = r['device_ms'], r['kernels_ms']
+    shares = 'not measured'
+    if k:
+      shares = ' / '.join('%.3f' % k.get(key, 0) for key in ('sync_settle', 'sync_scan', 'sync_emit')) + \
+          ' / %.3f / %.3f / %.3f' % (k.get('sync_serial', 0) + k.get('entropy', 0), k.get('idct', 0), k.get('rgb', 0))
     out.append('| %s | %s | %s | %d | %.3f (%.3f - %.3f) | %s | %s | %.1f | %.1f | %.1f | %.2fx |' %
-               (r['case'], r['files'], r['subsampling'], r['segments'], d['median'], d['min'], d['max'], r['measured'],
-                '%.3f / %.3f / %.3f' % (k.get('entropy', 0), k.get('idct', 0), k.get('rgb', 0)) if k else 'not measured',
+               (r['case'], r['files'], r['subsampling'], r['segments'], d['median'], d['min'], d['max'], r['measured'], shares,
                 r['of_copy'], r['from_file_bytes_ms'], r['pil_ms'], r['speedup_vs_pil']))
+  sync = [r for r in rows if 'sweep' in r]
+  if sync:
+    out += ['', 'Files without restart markers (DESIGN.md §3.36): the parallel walk at the default sub_bytes against the one-lane walk '
+            '(`--jpeg-serial-entropy`) on the same files in the same process, the info words (pictures by 0 a lane per segment / 1 verified '
+            'subsequences / 2 serial fallback) and the sweep of sub_bytes (device ms, info 1 / 2).', '',
+            '| pictures | sampling | device ms | one-lane ms | measured | one-lane / parallel | info 0 / 1 / 2 | ' +
+            ' | '.join('sub_bytes %d' % b for b in (64, 128, 256, 512)) + ' |', '|---|---|---|---|---|---|---|---|---|---|---|']
+    for r in sync:
+      cells = ['%.3f (%d / %d)' % (r['sweep'][str(b)]['ms'], r['sweep'][str(b)]['info']['1'], r['sweep'][str(b)]['info']['2']) for b in (64, 128, 256, 512)]
+      out.append('| %s | %s | %.3f | %.3f | %s | %.2fx | %d / %d / %d | %s |' %
+                 (r['case'], r['subsampling'], r['device_ms']['median'], r['serial_ms']['median'], r['serial_measured'],
+                  r['serial_ms']['median'] / r['device_ms']['median'], r['info']['0'], r['info']['1'], r['info']['2'], ' | '.join(cells)))
   text = '\n'.join(out) + '\n'
   if pack:
     text += '\n| %s | total ms | read ms | device ms |\n|---|---|---|---|\n' % pack['case']
